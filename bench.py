@@ -13,6 +13,11 @@ reference's DP byte-range split exchanges nothing).  torch.distributed is used
 only for the start/stop barriers and the max-over-ranks time.
 
 Output: one JSON line on rank 0 (see DESIGN.md "Measurement").
+
+A plain run generates the shard, warms up, times --steps steps and prints the
+line.  --full adds the context figures that take runs of their own (hbm_copy,
+cpu_baseline, cpu_baseline_max_threads); --dump-outputs DIR writes what the
+last timed step computed (dump_outputs below).
 """
 import argparse
 import json
@@ -227,6 +232,45 @@ def cpu_baseline(text, starts, fmt, budget_s, wide=False):
                          nproc, secs)}
 
 
+DUMP_SAMPLE = 1 << 20  # elements kept per dumped array: 7 arrays x 8 B x 2^20 = 56 MiB at the very most
+
+
+def dump_outputs(dirname, out, res):
+    """--dump-outputs: what the last timed step left in the caller's CSR
+    buffers, as <dirname>/<name>.npy.  The arrays are the ones parse_into's
+    caller receives (offset, label, weight, qid, field, index, value, each cut
+    to its count, and the call's result record); a slot whose count is 0 is
+    the caller's empty array and gets no file; float32 stays float32, integer
+    arrays are written as float64 (exact below 2^53).  An array longer than
+    DUMP_SAMPLE elements is written as a fixed sample: its elements at
+    DUMP_SAMPLE sorted positions drawn by numpy's default_rng(0), the same
+    positions for the same length in every run, gathered on the device."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    c = out["counts"]
+    lens = {"offset": c[dmlc_amd.ROWS] + 1, "label": c[dmlc_amd.LABEL], "weight": c[dmlc_amd.WEIGHT],
+            "qid": c[dmlc_amd.QID], "field": c[dmlc_amd.FIELD], "index": c[dmlc_amd.INDEX],
+            "value": c[dmlc_amd.VALUE]}
+    arrays = {"result": res[:12]}  # counts, error, path, max index / field of the last call
+    for k, n in lens.items():
+        if n == 0:  # a slot this input does not fill (libsvm: no field; no weight / qid): no file
+            if os.path.exists(os.path.join(dirname, k + ".npy")):
+                os.remove(os.path.join(dirname, k + ".npy"))
+            continue
+        a = out[k][:n]
+        if n > DUMP_SAMPLE:
+            pos = np.sort(np.random.default_rng(0).integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+            a = a[torch.from_numpy(pos).to(a.device)]
+        arrays[k] = a
+    for k, a in arrays.items():
+        h = a.cpu().numpy()
+        if k in ("offset", "qid"):
+            h = h.view(np.uint64)
+        elif k in ("field", "index"):
+            h = h.view(np.uint32 if h.dtype == np.int32 else np.uint64)
+        np.save(os.path.join(dirname, k + ".npy"), h if h.dtype == np.float32 else h.astype(np.float64))
+
+
 def spawn_ranks(n):
     """`bench.py --gpus N` without a launcher: start N rank processes (one per
     GPU) the way torch.distributed.run would, and exit with the first failing
@@ -259,10 +303,17 @@ def main():
     ap.add_argument("--rows", type=int, default=0, help="override rows per GPU")
     ap.add_argument("--tile-bytes", type=int, default=0)
     ap.add_argument("--label-column", type=int, default=-1, help="csv: CSVParserParam::label_column")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the context figures (rank 0, N=1): "
+                         "hbm_copy and the CPU baselines")
     ap.add_argument("--cpu-budget", type=float, default=15.0,
-                    help="seconds of CPU-baseline parsing (rank 0, N=1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="with --full: seconds of CPU-baseline parsing (rank 0, N=1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output arrays (rank 0's) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
@@ -364,6 +415,8 @@ def main():
         raise RuntimeError("parse error %#x" % int(r[8]))
     if int(r[9]) != gate:
         raise RuntimeError("path changed inside the timed region (%d -> %d)" % (gate, int(r[9])))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, res)
 
     ms_per_step = elapsed * 1e3 / args.steps
     total_in = nbytes * world
@@ -427,12 +480,13 @@ def main():
                          "launcher": "bench.py --gpus" if os.environ.get("DMLC_AMD_BENCH_SPAWNED") else "external",
                          "note": "one rank per GPU" if ndev >= world else
                                  "rehearsal: %d ranks share %d card(s), gloo barriers" % (world, ndev)}
-    if rank == 0 and world == 1:
+    # context figures that take runs of their own: only with --full
+    if args.full and rank == 0 and world == 1:
         try:
             line["hbm_copy"] = hbm_copy_rate(dev)
         except Exception as e:  # context only, never fatal
             line["hbm_copy"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             line["cpu_baseline"] = cpu_baseline(text, starts, pfmt, args.cpu_budget)
             if line["cpu_baseline"].get("kind") == "reference":

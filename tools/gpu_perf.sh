@@ -10,5 +10,5 @@ timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/pytest_gpu_$TAG.log 2
 tail -2 $O/pytest_gpu_$TAG.log
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python tools/stamps.py > $O/stamps_$TAG.log 2>&1 && cat $O/stamps_$TAG.log \
-  && timeout -k 10 600 python bench.py --no-cpu-baseline ${BENCH_ARGS} > $O/bench_$TAG.json 2> $O/bench_$TAG.err \
+  && timeout -k 10 600 python bench.py --full --no-cpu-baseline ${BENCH_ARGS} > $O/bench_$TAG.json 2> $O/bench_$TAG.err \
   && cat $O/bench_$TAG.json

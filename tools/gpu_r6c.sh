@@ -14,7 +14,7 @@ done
 for cfg in ${CCFGS:-csv csv_dirty}; do
   timeout -k 10 120 python tools/time_variant.py $cfg 2>&1 | grep -v amdgpu.ids | sed "s/^/$cfg /" | tee -a $O/time.txt || exit 1
 done
-timeout -k 10 300 python bench.py > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
 cat $O/bench.json
 if [ -n "$SUITE" ]; then
   timeout -k 10 1000 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $O/pytest.log 2>&1

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round evidence per bench config on the GPU box.  The bench line is the
 # output of the profiled run itself: rocprofv3 --kernel-trace --stats wraps
-# `bench.py --config <c>`, so profiles/<tag>_<c>_kernel_stats.csv and the line
+# `bench.py --full --config <c>`, so profiles/<tag>_<c>_kernel_stats.csv and the line
 # come from the same launches.  Then the PMC passes (tools/gpu_pmc.sh:
 # FETCH_SIZE, WRITE_SIZE, SQ) unless NO_PMC=1.
 #   TAG=r3 [NO_PMC=1] [NO_CPU=1] bash tools/profile_configs.sh libsvm_1m_x128 csv_1m_x256 ...
@@ -17,7 +17,7 @@ for c in "$@"; do
   [ -n "$NO_CPU" ] && extra="--no-cpu-baseline"
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$t -o run -- \
-    python3 $R/bench.py --config $c --cpu-budget ${CPU_BUDGET:-10} $extra ${BENCH_EXTRA} > $O/bench_$t.out 2> $O/bench_$t.err \
+    python3 $R/bench.py --full --config $c --cpu-budget ${CPU_BUDGET:-10} $extra ${BENCH_EXTRA} > $O/bench_$t.out 2> $O/bench_$t.err \
     || { tail -5 $O/bench_$t.err; exit 1; }
   grep '^{' $O/bench_$t.out | tail -1 > $O/bench_$t.json
   python3 -c "import json;d=json.load(open('$O/bench_$t.json'));print('$c', d['value'], d['ms_per_step'], d['roofline']['avg_ms'], d['roofline']['frac'], d['path'], (d.get('cpu_baseline') or {}).get('value'))"

@@ -11,7 +11,7 @@ mkdir -p $O
 for c in "$@"; do
   t=${TAG}_$c
   cd $R
-  timeout -k 10 900 python bench.py --config $c --cpu-budget ${CPU_BUDGET:-10} > $O/bench_$t.json 2> $O/bench_$t.err || { tail -5 $O/bench_$t.err; exit 1; }
+  timeout -k 10 900 python bench.py --full --config $c --cpu-budget ${CPU_BUDGET:-10} > $O/bench_$t.json 2> $O/bench_$t.err || { tail -5 $O/bench_$t.err; exit 1; }
   python -c "import json;d=json.load(open('$O/bench_$t.json'));print('$c', d['value'], d['roofline']['avg_ms'], d['roofline']['frac'], (d.get('cpu_baseline') or {}).get('value'))"
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$t -o run -- \
