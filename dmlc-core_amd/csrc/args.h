@@ -157,6 +157,7 @@ struct FastCsvArgs {
   uint32_t *gate;
   unsigned long long *err;
   uint64_t *res;
+  int ws;               // the delimiter is ' ' or '\t': the whitespace-mode kernels (csv_fast.h WS)
 };
 
 // Label / weight columns the single-pass CSV kernel takes: every row holds a
@@ -174,6 +175,32 @@ DA_HD bool csv_fast_columns_ok(int label_col, int weight_col) {
 // The single-pass integer-DType kernel: no label column; the weight column
 // is an ordinary column for integer DTypes (csv_parser.h:111-114).
 DA_HD bool csv_fast_int_ok(int label_col) { return label_col < 0; }
+
+// Delimiters the number decoders can consume (csv_parser.h:99-127): the
+// field structure then depends on decoding -- whitespace (strtof / strtoll
+// skip it; '\v' too), digits, letters, signs, '.', '_', '(', ')', NUL.  The
+// exact kernels walk such lines byte by byte (CsvArgs::fast_delim is false).
+DA_HD bool csv_delim_plain(uint32_t c) {
+  if (c == ' ' || (c >= '\t' && c <= '\r')) return false;
+  if ((c >= '0' && c <= '9') || ((c | 32u) >= 'a' && (c | 32u) <= 'z')) return false;
+  if (c == '+' || c == '-' || c == '.' || c == '_' || c == '(' || c == ')') return false;
+  return c != 0 && c < 0x100u;
+}
+// ' ' and '\t': the single pass takes them in its whitespace mode, where a
+// run of blanks holds at most one structural delimiter (csv_fast.h WS)
+DA_HD bool csv_delim_ws(uint32_t c) { return c == ' ' || c == '\t'; }
+// The single-pass decision for a delimiter: 0 the exact kernels, 1 the plain
+// kernels, 2 the whitespace-mode kernels
+DA_HD int csv_single_pass_delim(uint32_t c) { return csv_delim_plain(c) ? 1 : (csv_delim_ws(c) ? 2 : 0); }
+// Label / weight columns the single pass takes by DType (vtype 0 f32, else
+// int32 / int64).  Float values: csv_fast_columns_ok.  Integer values: the
+// weight column is an ordinary column and any label column stands -- label
+// column 0, where a one-field row is the reference's fatal "Delimiter not
+// found", is checked on the device as for floats (csv_fast.h labsum).
+// (csv_fast_int_ok keeps the plain integer kernel's form: no label column.)
+DA_HD bool csv_single_pass_columns(int vtype, int label_col, int weight_col) {
+  return vtype == 0 ? csv_fast_columns_ok(label_col, weight_col) : true;
+}
 
 struct CsvArgs {
   const uint8_t *text;

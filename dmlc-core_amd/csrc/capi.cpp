@@ -36,13 +36,8 @@ struct Carve {
 // structure depend on decoding (csv_parser.h:99-127): handled by the exact
 // per-line path instead of the field-parallel one.
 bool csv_delim_fast(int d, int vtype) {
-  const unsigned c = (unsigned)d & 0xFFu;
-  if (c == ' ' || (c >= '\t' && c <= '\r')) return false;  // whitespace (incl. \v for strtoll)
-  if ((c >= '0' && c <= '9') || ((c | 32u) >= 'a' && (c | 32u) <= 'z')) return false;
-  if (c == '+' || c == '-' || c == '.' || c == '_' || c == '(' || c == ')') return false;
-  if (c == 0) return false;
   (void)vtype;
-  return true;
+  return dmlc_amd::csv_delim_plain((unsigned)d & 0xFFu);  // args.h
 }
 
 // ---- kernel timing (dmlc_amd_profile_begin / _end)
@@ -345,13 +340,14 @@ int dmlc_amd_parse(const void *d_text, uint64_t nbytes, const uint64_t *d_chunk_
     f.gate = ctl;
     f.err = ferr;
     f.res = res;
-    // the uniform-grammar CSV kernels: float values with the label / weight
-    // columns they take, or integer values without a label column; a
-    // delimiter the number decoders cannot consume (csv_fast.h)
-    const bool cols_ok = prm->value_type == DMLC_AMD_F32
-                             ? dmlc_amd::csv_fast_columns_ok(prm->label_column, prm->weight_column)
-                             : dmlc_amd::csv_fast_int_ok(prm->label_column);
-    const bool use_fast = nbytes > 0 && cols_ok && a.fast_delim && !(prm->flags & DMLC_AMD_FLAG_EXACT);
+    // the uniform-grammar CSV kernels: the label / weight columns they take
+    // by DType, and a delimiter the number decoders cannot consume or ' ' /
+    // '\t' (the whitespace mode); a.fast_delim stays the exact kernels' own
+    // question (args.h csv_single_pass_*, csv_fast.h)
+    const int sp_delim = dmlc_amd::csv_single_pass_delim(a.delim);
+    f.ws = sp_delim == 2;
+    const bool cols_ok = dmlc_amd::csv_single_pass_columns(prm->value_type, prm->label_column, prm->weight_column);
+    const bool use_fast = nbytes > 0 && cols_ok && sp_delim != 0 && !(prm->flags & DMLC_AMD_FLAG_EXACT);
     e = dmlc_amd::launch_csv(a, f, use_fast, res, phase, s);
   } else {  // DMLC_AMD_LIBFM
     dmlc_amd::LibfmArgs a;

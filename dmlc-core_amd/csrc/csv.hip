@@ -50,6 +50,51 @@ __global__ void __launch_bounds__(fast::kFThreads, FCSV_MINW) csv_fast_tile_sp(F
   fcsv::tile<MODE, true, 0>(a, sh, bk, blockIdx.x);
 }
 
+// the whitespace-mode forms (delimiter ' ' or '\t', FastCsvArgs::ws) and the
+// integer label form (csv_fast.h tile<MODE, SP, VT, WS>): same launch bounds
+// and LDS as the three above
+#define FCSV_KERNEL(NAME, SP, VT, WS)                                                       \
+  template <int MODE>                                                                       \
+  __global__ void __launch_bounds__(fast::kFThreads, FCSV_MINW) NAME(FastCsvArgs a) {       \
+    __shared__ __attribute__((aligned(16))) fcsv::Shared sh;                                \
+    __shared__ uint64_t scratch[kSmallScratchU64];                                          \
+    DevBlockS bk{scratch};                                                                  \
+    fcsv::tile<MODE, SP, VT, WS>(a, sh, bk, blockIdx.x);                                    \
+  }
+FCSV_KERNEL(csv_fast_tile_ws, false, 0, true)
+FCSV_KERNEL(csv_fast_tile_int_ws, false, 1, true)
+FCSV_KERNEL(csv_fast_tile_sp_ws, true, 0, true)
+FCSV_KERNEL(csv_fast_tile_int_sp, true, 1, false)
+FCSV_KERNEL(csv_fast_tile_int_sp_ws, true, 1, true)
+#undef FCSV_KERNEL
+
+// the single-pass kernel of a call: by DType, label / weight columns and
+// delimiter kind; the profile marks carry the name of the kernel that ran
+template <int MODE>
+void launch_fast_tile(const FastCsvArgs &f, bool sp, hipStream_t s) {
+  const bool iv = f.vtype != 0, ws = f.ws != 0;
+  const dim3 g(f.ntiles), b(fast::kFThreads);
+#define FCSV_GO(NAME)                                           \
+  do {                                                          \
+    const char *nm = MODE == 1 ? #NAME "<1>" : #NAME "<2>";     \
+    prof_mark(0, s, nm);                                        \
+    NAME<MODE><<<g, b, 0, s>>>(f);                              \
+    prof_mark(1, s, nm);                                        \
+    return;                                                     \
+  } while (0)
+  if (ws) {
+    if (iv && sp) FCSV_GO(csv_fast_tile_int_sp_ws);
+    if (iv) FCSV_GO(csv_fast_tile_int_ws);
+    if (sp) FCSV_GO(csv_fast_tile_sp_ws);
+    FCSV_GO(csv_fast_tile_ws);
+  }
+  if (iv && sp) FCSV_GO(csv_fast_tile_int_sp);
+  if (iv) FCSV_GO(csv_fast_tile_int);
+  if (sp) FCSV_GO(csv_fast_tile_sp);
+  FCSV_GO(csv_fast_tile);
+#undef FCSV_GO
+}
+
 // fill phase after a count phase that fell back to the exact kernels: reopen
 // the first-error word so the write pass can record it, and store the closing
 // offset (the reference's final push) the size query could not
@@ -97,20 +142,8 @@ hipError_t launch_csv(const CsvArgs &a, const FastCsvArgs &f, bool use_fast, uin
   if (!a.ntiles && phase != kPhaseCount) fl.add(reinterpret_cast<uint64_t *>(a.offset), 1, 0);  // empty input: offset = {0}
   if ((e = launch_prologue(fl, s)) != hipSuccess) return e;
   if (use_fast) {
-    const bool iv = f.vtype != 0;
-    if (phase == kPhaseCount) {
-      prof_mark(0, s, iv ? "csv_fast_tile_int<1>" : "csv_fast_tile<1>");
-      if (iv) csv_fast_tile_int<1><<<f.ntiles, fast::kFThreads, 0, s>>>(f);
-      else if (sp) csv_fast_tile_sp<1><<<f.ntiles, fast::kFThreads, 0, s>>>(f);
-      else csv_fast_tile<1><<<f.ntiles, fast::kFThreads, 0, s>>>(f);
-      prof_mark(1, s, "csv_fast_tile<1>");
-    } else {
-      prof_mark(0, s, iv ? "csv_fast_tile_int<2>" : "csv_fast_tile<2>");
-      if (iv) csv_fast_tile_int<2><<<f.ntiles, fast::kFThreads, 0, s>>>(f);
-      else if (sp) csv_fast_tile_sp<2><<<f.ntiles, fast::kFThreads, 0, s>>>(f);
-      else csv_fast_tile<2><<<f.ntiles, fast::kFThreads, 0, s>>>(f);
-      prof_mark(1, s, "csv_fast_tile<2>");
-    }
+    if (phase == kPhaseCount) launch_fast_tile<1>(f, sp, s);
+    else launch_fast_tile<2>(f, sp, s);
     if (sp) label_check_kernel<<<1, kLabShards, 0, s>>>(f.labsum, gate);
   }
   // ---- exact path, gated on the device flag (early exit when the fast path stood)

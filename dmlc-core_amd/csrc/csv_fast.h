@@ -19,6 +19,8 @@
 // Values use the 32-bit window decoder (fast_common.h wfloat32) with the
 // exact byte decoder as fallback.  Any byte outside the grammar sets the gate
 // word and the exact tile kernels (csv_core.h) produce the result.
+// Instantiations of the one tile body add label / weight columns (SP),
+// integer values (VT) and ' ' / '\t' as the delimiter (WS); see tile().
 //
 // Same structure and block policy as svm_fast.h (the CPU emulator runs it).
 #pragma once
@@ -121,8 +123,12 @@ DA_HD bool inf_nan_of(const uint32_t w[4], float *v) {
 }
 // junk: with the junk class (digit + newline, a pair no other byte has; the
 // classifier splits it off)
-DA_HD uint32_t class_of_csv(uint32_t b, uint32_t delim, bool blanks, bool junk = false) {
+// ws: the delimiter is ' ' or '\t' (the whitespace mode, tile<.., WS>): it
+// keeps the delimiter class and the other of the two is a blank -- outside
+// the grammar where that has no blanks (the label / weight kernels)
+DA_HD uint32_t class_of_csv(uint32_t b, uint32_t delim, bool blanks, bool junk = false, bool ws = false) {
   if (b == delim) return 0x01000000u;
+  if (ws && (b == ' ' || b == '\t')) return blanks ? 0u : 0x00000100u;
   if (is_digitchar(b)) return is_digit(b) ? 0x00000101u : 0x00000001u;
   if (b == '\n' || b == '\r') return 0x00010000u;
   if (blanks && (b == ' ' || b == '\t')) return 0u;  // blank: class 0
@@ -249,9 +255,22 @@ DA_HD int64_t wint64m(const uint32_t w[4], uint32_t M, bool *ok) {
 // SP: label / weight columns may be set (a separate kernel, so the plain
 // form carries none of their code); blanks are outside its grammar.
 // VT: 0 float values (ParseFloat), 1 integer values (strtoll base 0, int32 /
-// int64 by a.vtype; no label column, the weight column is a plain column for
-// integer DTypes, csv_parser.h:111-114).
-template <int MODE, bool SP, int VT, class BK>
+// int64 by a.vtype; the weight column is a plain column for integer DTypes,
+// csv_parser.h:111-114; with SP the label column holds a DType too: decoded
+// by strtoll and stored as int32 / int64).
+// WS: the delimiter is ' ' or '\t' (FastCsvArgs::ws).  strtof / strtoll skip
+// blanks at a field start and the delimiter is one, so of a maximal run of
+// ' ' / '\t' bytes inside a row (a blank run) only one byte separates fields:
+//   - in a run that follows a non-blank byte of its row, the first delimiter
+//     byte is structural: the column advances, the next field starts after it
+//     (csv_parser.h:123-135 walks from the number's end to the next delimiter);
+//   - every other delimiter byte of the run is an ordinary blank;
+//   - a run at a row start or a chunk start has no structural delimiter (the
+//     first field's decoder skips it); a chunk start inside a run ends it.
+// After that reclassification the blank rules below hold unchanged.  The
+// label / weight kernels (SP, no blanks in their grammar) take clean input
+// only: a number character after every delimiter, no delimiter at a row start.
+template <int MODE, bool SP, int VT, bool WS = false, class BK>
 DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
   // Tile k = workgroup k (its blockIdx).  The look-back needs every tile's
   // predecessors to become resident eventually; workgroups are dispatched in
@@ -283,7 +302,7 @@ DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
     sh.nlab = sh.nfirst = 0;
     sh.junk = 0;
   }
-  for (int i = tid; i < kClsEntries; i += kFThreads) sh.cls[i] = class_of_csv((uint32_t)i, a.delim, !SP, JK);
+  for (int i = tid; i < kClsEntries; i += kFThreads) sh.cls[i] = class_of_csv((uint32_t)i, a.delim, !SP, JK, WS);
   init_dec_tables(sh.dt, bk);
   stage_commit(a.text, a.n, t.tlo, sr, sh.c, bk);
   bk.sync();
@@ -350,7 +369,62 @@ DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
     }
     const uint64_t n1 = sh.u.m.n[tid], l1 = sh.u.m.l[tid];
     RS = ~N & valid & ((N << 1) | (n1 >> 63) | S);
-    const uint64_t FSd = ((L << 1) | (l1 >> 63)) & ~N & ~S & valid;
+    uint32_t ltop = (uint32_t)(l1 >> 63);  // a field starts at my first byte
+    uint32_t wcin = 0;                     // WS: the blank carry into my segment (cin below)
+    if constexpr (WS && !SP) {
+      // ---- the structural delimiters (WS above): L holds every delimiter
+      // byte; keep the first of each blank run that follows a non-blank byte
+      // of its row.  "No delimiter yet" is carried from the run's first byte
+      // through the other blank (Pm) to the byte it lands on -- the idiom of
+      // `land` below.  What the segment before hands over is read off its
+      // planes: its trailing blank run is a leading run (after a newline or
+      // with a chunk start inside: the first field starts in it, wcin), has
+      // spent its delimiter (wcin, or ltop when that is its last byte), or
+      // has none yet (wopen).
+      uint32_t wopen = 0, wtop_nb = 0;
+      ltop = 0;
+      if (P > 0 && !(S & 1u)) {
+        uint64_t nb1 = sh.u.m.d[tid] | n1;  // bytes of the segment before that are no ' ' / '\t'
+        if (JK && !(nb1 >> 63) && sh.junk) {
+          // its junk bytes are not in the planes: its trailing blanks from its bytes
+          const uint8_t *prev = sh.c.text + kPre + (tid - 1) * kSegB;
+          int j = 63;
+          while (j >= 0 && (prev[j] == ' ' || prev[j] == '\t')) --j;
+          if (j >= 0) nb1 |= 1ull << j;
+        }
+        if (nb1 >> 63) {
+          wtop_nb = (uint32_t)(~n1 >> 63);  // a run starting at my first byte follows a non-blank byte
+        } else if (!nb1) {
+          bad = 1;  // 64 blanks in a row: beyond this carry, the exact kernels take it
+        } else {
+          const uint32_t j = 63u - (uint32_t)clz64(nb1);
+          const uint64_t x0 = P - 64u + j + 1u;  // the trailing run's first byte
+          bool cs = x0 <= sh.c.cfloor && sh.c.cfloor < P;  // a chunk (and row) starts inside the run
+          for (uint32_t i = 0; i < sh.c.ncs; ++i) cs = cs || (x0 <= sh.c.csl[i] && sh.c.csl[i] < P);
+          const uint64_t lrun = l1 >> (j + 1u);  // the run's delimiter bytes
+          if (((n1 >> j) & 1u) || cs) wcin = 1u;
+          else if (!lrun) wopen = 1u;
+          else if (lrun == 1ull << (62u - j)) ltop = 1u;  // its last byte is its only delimiter
+          else wcin = 1u;
+        }
+      }
+      const uint64_t NB = (D | J) & valid, Wm = ~(D | N | J) & valid;
+      const uint64_t A = Wm & ((NB << 1) | wtop_nb) & ~S;  // runs that follow a non-blank byte of their row
+      const uint64_t Pm = Wm & ~L & ~S;
+      uint32_t c0;
+      const uint64_t lnd = add_carry(Pm, A & Pm, wopen, &c0) & ~Pm;
+      L &= (A | lnd) & ~S;
+    }
+    if constexpr (WS && SP) {
+      // clean input only: a number character of the same chunk after every
+      // delimiter, no delimiter at a row start -- then every delimiter is
+      // structural and no field starts with a blank
+      uint64_t nx = D >> 1;
+      if ((L >> 63) && P + 64 < a.n && !t.is_cs(P + 64) && is_digitchar(sh.c.text[kPre + (tid + 1) * kSegB]))
+        nx |= 1ull << 63;
+      if ((L & ~nx) | (L & (S >> 1)) | (RS & L)) bad = 1;
+    }
+    const uint64_t FSd = ((L << 1) | ltop) & ~N & ~S & valid;
     uint64_t F = RS | FSd;  // field starts
     if (JK && sh.junk) {  // block-uniform
       // a UTF-8 BOM at a row start (IgnoreUTF8BOM, text_parser.h:83-102):
@@ -366,6 +440,7 @@ DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
       for (uint64_t m = RS & J; m; m &= m - 1) {
         const uint32_t i = (uint32_t)ctz64(m);
         if (!is_bom((int)i)) continue;
+        if constexpr (WS) bad = 1;  // (a blank run after the BOM would be a leading run: the exact kernels)
         const uint64_t bit = m & (0 - m);
         F &= ~bit;
         if (i <= 60u) {
@@ -393,8 +468,21 @@ DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
         else F |= 1ull << j;
       }
     }
-    if constexpr (SP) {
+    if constexpr (SP && VT == 0) {
       T = F & D;
+    } else if constexpr (SP) {
+      // strtoll consumed nothing unless a digit follows the optional sign (as
+      // below): such a field is no value, and as the label column the
+      // reference's pushed 0 -- the label check hands it to the exact kernels
+      const uint64_t C = F & D;
+      const uint64_t G = (uint64_t)sh.gw[2 * tid] | ((uint64_t)sh.gw[2 * tid + 1] << 32);
+      const uint64_t Gn = ((G >> 1) | ((uint64_t)(sh.gw[2 * tid + 2] & 1u) << 63)) & ~(S >> 1) &
+                          ~((uint64_t)t.is_cs(P + 64) << 63);
+      T = C & G;
+      for (uint64_t m = C & ~G & Gn; m; m &= m - 1) {
+        const uint32_t b = sh.c.text[kPre + tid * kSegB + ctz64(m)];
+        if (b == '-' || b == '+') T |= m & (0 - m);
+      }
     } else {
       // Blanks (' ', '\t', class 0): ParseFloat / strtoll skip them at a field
       // start (strtonum.h:95-264), so a field's token is the first non-blank
@@ -405,8 +493,8 @@ DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
       // A chunk start ends a blank run (the decoder would read past the
       // chunk: bad) and, when blank, starts a run of its own (X).
       const uint64_t B = ~(D | N | L | J) & valid, Bs = B & ~S, X = F & B & S;
-      uint32_t cin = 0;
-      if (P > 0 && !(S & 1u)) {
+      uint32_t cin = wcin;
+      if (!WS && P > 0 && !(S & 1u)) {
         uint64_t nb1 = sh.u.m.d[tid] | n1 | l1;  // non-blank bytes of the segment before
         if (JK && !(nb1 >> 63) && sh.junk) {
           // its junk bytes are not in the planes: its trailing blanks from its bytes
@@ -475,6 +563,12 @@ DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
           const uint32_t b = sh.c.text[kPre + tid * kSegB + ctz64(m)];
           if (b == '-' || b == '+') T |= m & (0 - m);
         }
+        // WS: a strtoll that converts nothing hands back the field's start,
+        // before the blanks it skipped (strtof keeps them) -- and the
+        // reference then finds the next delimiter among those blanks
+        // (csv_parser.h:123-127): the exact kernels
+        if constexpr (WS)
+          if (land & D & ~T) bad = 1;
       }
     }
   }
@@ -695,14 +789,21 @@ DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
       const uint64_t bit = 1ull << b;
       const uint64_t row = eR + popc64(RS & ((bit - 1) | bit)) - 1;  // this token's row
       if (c == Lc) {
-        if (row < a.cap[C_LABEL]) a.label[row] = v;
-        else raise_error(a.err, E_CAPACITY, P + b);
+        if (row < a.cap[C_LABEL]) {
+          if constexpr (VT == 0) a.label[row] = v;
+          else if (a.vtype == 1) reinterpret_cast<int32_t *>(a.label)[row] = (int32_t)v;  // the label is a DType
+          else reinterpret_cast<int64_t *>(a.label)[row] = v;
+        } else {
+          raise_error(a.err, E_CAPACITY, P + b);
+        }
         return;
       }
-      if (c == Wc) {
-        if (row < a.cap[C_WEIGHT]) a.weight[row] = v;
-        else raise_error(a.err, E_CAPACITY, P + b);
-        return;
+      if constexpr (VT == 0) {  // (an ordinary column for integer DTypes)
+        if (c == Wc) {
+          if (row < a.cap[C_WEIGHT]) a.weight[row] = v;
+          else raise_error(a.err, E_CAPACITY, P + b);
+          return;
+        }
       }
       g -= row * nsp + sp_before;  // labels and weights before this token
     }

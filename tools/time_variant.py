@@ -24,14 +24,23 @@ fmt, rows, width, kind = {"libsvm": ("libsvm", 1 << 20, 128, synth.LIBSVM), "csv
                           "csv_nan": ("csv", 1 << 20, 256, synth.CSV_NAN),
                           "exact": ("libsvm", 1 << 20, 128, synth.LIBSVM),
                           "csv_exact": ("csv", 1 << 20, 256, synth.CSV),
-                          "libfm_exact": ("libfm", 1 << 20, 64, synth.LIBFM)}[cfg]
+                          "libfm_exact": ("libfm", 1 << 20, 64, synth.LIBFM),
+                          # config 3's text with another delimiter / DType / label column (csv_fast.h WS, int label)
+                          "csv_tsv": ("csv", 1 << 20, 256, synth.CSV), "csv_ssv": ("csv", 1 << 20, 256, synth.CSV),
+                          "csv_i32_label0": ("csv", 1 << 20, 256, synth.CSV),
+                          "csv_tsv_label0": ("csv", 1 << 20, 256, synth.CSV)}[cfg]
+pkw = {"csv_tsv": {"delimiter": "\t"}, "csv_ssv": {"delimiter": " "},
+       "csv_i32_label0": {"value_type": "i32", "label_column": 0},
+       "csv_tsv_label0": {"delimiter": "\t", "label_column": 0}}.get(cfg, {})
 text, _ = synth.rows(kind, rows, width, seed=1)
+if pkw.get("delimiter", ",") != ",":
+    text = np.where(text == ord(","), np.uint8(ord(pkw["delimiter"])), text).astype(np.uint8)
 starts = dmlc_amd.text_chunk_starts(text)
 dev = torch.device("cuda", 0)
 d_text = torch.from_numpy(text).to(dev)
 d_starts = torch.from_numpy(starts).to(dev)
 p = dmlc_amd.DeviceParser(fmt, flags=dmlc_amd.FLAG_EXACT if cfg.endswith("exact") else 0,
-                          tile_bytes=int(os.environ.get("TILE_BYTES", "0")))
+                          tile_bytes=int(os.environ.get("TILE_BYTES", "0")), **pkw)
 res = torch.zeros(16, dtype=torch.int64, device=dev)
 counts = p.count(d_text, d_starts, result=res)
 out = p.alloc(counts)
@@ -47,6 +56,6 @@ torch.cuda.synchronize()
 call_ms = (time.perf_counter() - t0) * 100.0  # per call, whole pipeline
 ms, n, name = dmlc_amd.profile_end()
 r = res.cpu().numpy().view(np.uint64)
-print("tile=%s %s %s %.4f ms call %.3f ms path=%d err=%#x res15=%d" % (os.environ.get("TILE_BYTES", "0"),
+print("%s tile=%s %s %s %.4f ms call %.3f ms path=%d err=%#x res15=%d" % (cfg, os.environ.get("TILE_BYTES", "0"),
                                                           os.path.basename(os.environ.get("DMLC_AMD_LIB", "default")),
                                                   name, ms / max(n, 1), call_ms, int(r[9]), int(r[8]), int(r[15])))
