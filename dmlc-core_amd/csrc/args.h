@@ -161,7 +161,8 @@ struct FastCsvArgs {
 };
 
 // Label / weight columns the single-pass CSV kernel takes: every row holds a
-// non-empty field at each (checked on the device), and then a row always keeps
+// field at each (non-empty for integer values and in the whitespace mode;
+// checked on the device, csv_fast.h), and then a row always keeps
 // a non-special field -- unless the special columns are {0} or {0, 1}, where a
 // row of only those fields is the reference's fatal "Delimiter not found"
 // (csv_parser.h:128-132): label column 0 alone is checked on the device, the

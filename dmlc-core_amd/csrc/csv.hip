@@ -104,9 +104,9 @@ __global__ void reopen_kernel(uint64_t *res, uint64_t *offset, uint64_t cap_rows
   if (offset && res[0] < cap_rows + 1) offset[res[0]] = res[1];
 }
 
-// label column: the single pass assumed one non-empty label field per row
-// (and, for column 0, a delimiter in every row); a nonzero check sum hands the
-// input to the exact kernels
+// label / weight columns: the single pass assumed one label (weight) entry per
+// row (and, for label column 0, a delimiter in every row); a nonzero check sum
+// hands the input to the exact kernels
 __global__ void label_check_kernel(const uint64_t *labsum, uint32_t *gate) {
   const uint32_t i = threadIdx.x;  // kLabShards threads, one wave
   uint64_t a = labsum[i * 8], b = labsum[i * 8 + 1], c = labsum[i * 8 + 2];

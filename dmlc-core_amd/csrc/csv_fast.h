@@ -21,6 +21,11 @@
 // word and the exact tile kernels (csv_core.h) produce the result.
 // Instantiations of the one tile body add label / weight columns (SP),
 // integer values (VT) and ' ' / '\t' as the delimiter (WS); see tile().
+// Float values also take text fields, inf / nan, blanks and BOMs (the "junk"
+// rules below) -- with label / weight columns too, where the field at a
+// special column is that column's entry whether or not it holds a token (TX
+// in tile()); only the whitespace-mode label / weight kernel takes clean
+// input only.
 //
 // Same structure and block policy as svm_fast.h (the CPU emulator runs it).
 #pragma once
@@ -67,7 +72,7 @@ struct Shared {  // LDS of one workgroup
   uint32_t junk;  // the tile (or its halos) holds junk bytes (csv_junk_byte)
 };
 
-// "Junk" (float values, no label / weight column): text a number ends at
+// "Junk" (float values; not the whitespace-mode label / weight kernel): text a number ends at
 // (strtonum.h:95-264) -- a header word, a text column, "3.5kg", bytes >=
 // 0x80.  A field that starts with it holds no value (ParseFloat consumed
 // nothing: the column advances, csv_parser.h:115-118) -- except where
@@ -253,7 +258,10 @@ DA_HD int64_t wint64m(const uint32_t w[4], uint32_t M, bool *ok) {
 
 // MODE 1: count only (size query); MODE 2: parse and write.
 // SP: label / weight columns may be set (a separate kernel, so the plain
-// form carries none of their code); blanks are outside its grammar.
+// form carries none of their code).  For float values with a plain delimiter
+// it has the plain kernel's grammar (text, blanks, BOMs) and counts special
+// columns per field (TX below); for integer values and in the whitespace mode
+// blanks and text are outside its grammar.
 // VT: 0 float values (ParseFloat), 1 integer values (strtoll base 0, int32 /
 // int64 by a.vtype; the weight column is a plain column for integer DTypes,
 // csv_parser.h:111-114; with SP the label column holds a DType too: decoded
@@ -268,8 +276,9 @@ DA_HD int64_t wint64m(const uint32_t w[4], uint32_t M, bool *ok) {
 //   - a run at a row start or a chunk start has no structural delimiter (the
 //     first field's decoder skips it); a chunk start inside a run ends it.
 // After that reclassification the blank rules below hold unchanged.  The
-// label / weight kernels (SP, no blanks in their grammar) take clean input
-// only: a number character after every delimiter, no delimiter at a row start.
+// whitespace-mode label / weight kernels (SP && WS, no blanks in their grammar)
+// take clean input only: a number character after every delimiter, no
+// delimiter at a row start.
 template <int MODE, bool SP, int VT, bool WS = false, class BK>
 DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
   // Tile k = workgroup k (its blockIdx).  The look-back needs every tile's
@@ -280,7 +289,10 @@ DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
   // capped the 131k-tile launch at ~1.5 ms.)  Should a predecessor ever not
   // publish, kSpinLimit bounds the wait and the exact kernels take over.
   const int tid = bk.tid();
-  constexpr bool JK = VT == 0 && !SP;  // junk fields in the grammar (csv_junk_byte)
+  constexpr bool JK = VT == 0 && !(SP && WS);  // junk fields in the grammar (csv_junk_byte)
+  // float label / weight columns with text, blanks and BOMs (the field-based
+  // special-column rule below); the whitespace-mode form keeps clean input
+  constexpr bool TX = SP && VT == 0 && !WS;
   if (a.skip_if_gated && *a.gate) return;  // fill phase after an exact-path count: block-uniform
   FAST_STAMP(k, 0);
   FAST_STAMP(k, 1);
@@ -301,8 +313,10 @@ DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
     sh.u.m.d[0] = sh.u.m.n[0] = sh.u.m.l[0] = 0;
     sh.nlab = sh.nfirst = 0;
     sh.junk = 0;
+    if (TX) sh.npass = 0;  // (TX: "a carried-in tokenless field awaits its column", see below)
   }
-  for (int i = tid; i < kClsEntries; i += kFThreads) sh.cls[i] = class_of_csv((uint32_t)i, a.delim, !SP, JK, WS);
+  for (int i = tid; i < kClsEntries; i += kFThreads)
+    sh.cls[i] = class_of_csv((uint32_t)i, a.delim, !(SP && (WS || VT != 0)), JK, WS);
   init_dec_tables(sh.dt, bk);
   stage_commit(a.text, a.n, t.tlo, sr, sh.c, bk);
   bk.sync();
@@ -357,6 +371,7 @@ DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
   // ---- rows, fields, tokens of my segment
   const uint64_t P = t.tlo + (uint64_t)tid * kSegB;
   uint64_t RS = 0, T = 0, L = 0;
+  uint64_t Cc = 0;  // TX: tokenless field starts whose column the tile scan brings
   if (P < a.n) {
     const int nv = (int)mn<uint64_t>(64, a.n - P);
     const uint64_t valid = nv == 64 ? ~0ull : ((1ull << nv) - 1);
@@ -426,6 +441,7 @@ DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
     }
     const uint64_t FSd = ((L << 1) | ltop) & ~N & ~S & valid;
     uint64_t F = RS | FSd;  // field starts
+    uint64_t FB = 0;        // (TX) those behind a BOM that began in the segment before: column 0
     if (JK && sh.junk) {  // block-uniform
       // a UTF-8 BOM at a row start (IgnoreUTF8BOM, text_parser.h:83-102):
       // the row's first field starts after it -- in this segment, or in the
@@ -465,12 +481,12 @@ DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
         bool cs_in = (S & ((2ull << j) - 1)) != 0;  // a chunk start inside the BOM or right after it
         for (uint64_t y = x + 1; y < P; ++y) cs_in = cs_in || y == sh.c.cfloor || t.is_cs(y);
         if (cs_in || (((N | ~valid) >> j) & 1u)) bad = 1;
-        else F |= 1ull << j;
+        else F |= 1ull << j, FB |= 1ull << j;
       }
     }
-    if constexpr (SP && VT == 0) {
+    if constexpr (SP && VT == 0 && WS) {
       T = F & D;
-    } else if constexpr (SP) {
+    } else if constexpr (SP && VT != 0) {
       // strtoll consumed nothing unless a digit follows the optional sign (as
       // below): such a field is no value, and as the label column the
       // reference's pushed 0 -- the label check hands it to the exact kernels
@@ -522,6 +538,12 @@ DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
                 if (pb == '\n' || pb == '\r' || xb == sh.c.cfloor || t.is_cs(xb)) cin = 1u;
               }
             }
+            // the run's 62 or 63 blanks follow what may be the tail of a BOM
+            // that began in the segment before that one: the exact kernels
+            if (JK && !cin && j < 2u && sh.junk) {
+              const uint8_t *prev = sh.c.text + kPre + (tid - 1) * kSegB;
+              if (prev[j] == 0xBFu && (j == 0u || prev[0] == 0xBBu)) bad = 1;
+            }
           }
         }
       }
@@ -571,6 +593,32 @@ DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
           if (land & D & ~T) bad = 1;
       }
     }
+    if constexpr (TX) {
+      // The field at a special column is that column's entry whether or not
+      // ParseFloat read anything (csv_parser.h:111-114): a tokenless field
+      // there -- empty (its field start is the delimiter that ends it) or
+      // starting with text ParseFloat does not read -- becomes a pseudo-token,
+      // and the rank arithmetic below stays per token; the decoders yield its
+      // 0 as they do for a blank field and for text after blanks.  Its column
+      // is known here when its row starts in this segment or it stands behind
+      // a BOM; otherwise the tile scan brings it (Cc, resolved after the scan).
+      // A field of the row carried in follows a delimiter: its column is
+      // >= max(1, delimiters of this tile before it), so with label column 0
+      // alone it is never special.
+      const int lc = a.label_col, wc = a.weight_col;
+      for (uint64_t m = F & (L | J) & ~T; m; m &= m - 1) {
+        const uint64_t bit = m & (0 - m), below = bit - 1, r = RS & (below | bit);
+        int col = 0;
+        if (r) col = popc64(L & below & (~0ull << (63 - clz64(r))));
+        else if (!(FB & bit)) {
+          Cc |= bit;
+          continue;
+        }
+        if (col == lc || col == wc) T |= bit;
+      }
+      if ((lc > wc ? lc : wc) < 1) Cc = 0;
+      if (Cc) sh.npass = 1;
+    }
   }
   if (bad) atomic_or_u32(&sh.c.bad, 1u);
   // segmented delimiter count of my segment: since my last row start, or all
@@ -580,7 +628,30 @@ DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
   const uint64_t mine = (uint64_t)popc64(RS) | ((uint64_t)popc64(T) << 16) | ((uint64_t)tailc << 32) |
                         ((uint64_t)has_rs << 63);
   uint64_t totp;
-  const uint64_t ex = bk.exclusive(mine, (uint64_t)0, CsvScanOp(), &totp);
+  uint64_t ex = bk.exclusive(mine, (uint64_t)0, CsvScanOp(), &totp);
+  if constexpr (TX) {
+    if (sh.npass) {  // block-uniform: only tiles that hold such a field scan twice
+      // the scan's segmented count gives a carried-in field its column when
+      // its row starts in this tile.  When it starts before the tile the
+      // column is (delimiters of the row before the tile) + j and known only
+      // after the look-back, but the counts must be published before it: the
+      // tile declines unless max(1, j) is past both special columns.
+      const int lc = a.label_col, wc = a.weight_col, M = lc > wc ? lc : wc;
+      uint64_t add = 0;
+      for (uint64_t m = Cc; m; m &= m - 1) {
+        const uint64_t bit = m & (0 - m);
+        const int j = (int)((ex >> 32) & 0x7FFFFFFFu) + popc64(L & (bit - 1));
+        if (ex >> 63) {
+          if (j == lc || j == wc) add |= bit;
+        } else if ((j > 1 ? j : 1) <= M) {
+          atomic_or_u32(&sh.c.bad, 1u);
+        }
+      }
+      T |= add;
+      const uint64_t mine2 = (mine & ~(0xFFFFull << 16)) | ((uint64_t)popc64(T) << 16);
+      ex = bk.exclusive(mine2, (uint64_t)0, CsvScanOp(), &totp);
+    }
+  }
   const uint32_t nR = (uint32_t)(totp & 0xFFFF), nT = (uint32_t)((totp >> 16) & 0xFFFF);
   const uint32_t cnt4[4] = {nR, nT, (uint32_t)((totp >> 32) & 0x7FFFFFFF), (uint32_t)(totp >> 63)};
   if (tid == 0) {
@@ -719,8 +790,9 @@ DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
   const uint64_t bRows = sh.c.base[Q_ROWS], bVal = sh.c.base[Q_VALS], tcarry = sh.segc;
   // With a label column (csv_parser.h:111-112) the field at column label_col
   // of every row is its label and the other fields keep their column minus one
-  // past it.  The single pass assumes every row holds exactly one non-empty
-  // label field (then labels = rows and a token's value rank is its token rank
+  // past it.  The single pass assumes every row holds exactly one label token
+  // (TX: pseudo-tokens included, so one field at the label column; otherwise a
+  // non-empty label field -- then labels = rows and a token's value rank is its token rank
   // minus the labels before it) and checks that assumption: the tiles sum
   // (label tokens - rows) and, for label_col 0 (where a row without a
   // delimiter is the reference's fatal "Delimiter not found",
@@ -739,7 +811,23 @@ DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
   };
   if (has_sp) {
     uint32_t nl = 0, nf = 0, nw = 0;
-    if (has_lab && Lc == 0) {
+    if (TX && has_lab && Lc == 0) {
+      // column-0 labels: the tokens (pseudo-tokens included) from a row start
+      // through the row's first delimiter -- behind blanks or a BOM the label
+      // does not stand at the row start, and an empty one is that delimiter
+      const uint64_t fr = RS & (0ull - RS), lim = fr ? fr - 1 : ~0ull;
+      if (carry == 0) {  // the row carried in has no delimiter yet
+        const uint64_t fl = L & lim;
+        nf = fl != 0;
+        nl = (uint32_t)popc64(T & lim & (fl ? ((fl & (0ull - fl)) << 1) - 1 : ~0ull));
+      }
+      for (uint64_t rs = RS; rs; rs &= rs - 1) {
+        const uint64_t r = rs & (0ull - rs), nx = (rs & (rs - 1)) & (0ull - (rs & (rs - 1)));
+        const uint64_t span = (nx ? nx - 1 : ~0ull) & ~(r - 1), fl = L & span;
+        nf += fl != 0;
+        nl += (uint32_t)popc64(T & span & (fl ? ((fl & (0ull - fl)) << 1) - 1 : ~0ull));
+      }
+    } else if (has_lab && Lc == 0) {
       // column-0 labels are the row starts holding a token; a row's first
       // delimiter is the first after its start (row starts are sparse)
       nl = (uint32_t)popc64(RS & T);
@@ -753,7 +841,20 @@ DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
       for (uint64_t m = T; m; m &= m - 1) nl += col_of((uint32_t)ctz64(m)) == Lc;
     }
     if (has_w)
-      for (uint64_t m = T; m; m &= m - 1) nw += col_of((uint32_t)ctz64(m)) == Wc;
+      for (uint64_t m = T; m; m &= m - 1) {
+        const uint32_t b = (uint32_t)ctz64(m);
+        if (col_of(b) != Wc) continue;
+        ++nw;
+        if (TX && junk_tile) {
+          // a weight that reads as NaN ("nan", "-nan", "NaN(chars)", any case)
+          // is a missing weight (csv_parser.h:142): the exact kernels.  From
+          // the bytes, so the size query and the fill decide alike.
+          const uint8_t *p = sh.c.text + kPre + tid * kSegB + b;
+          const uint32_t sg = (*p == '-' || *p == '+') ? 1u : 0u;
+          const uint64_t q = P + b + sg, lim = t.next_cs(P + b);
+          if (q < lim && csv_inf_nan(p + sg, lim - q) >= 2u) atomic_or_u32(a.gate, 1u);
+        }
+      }
     if (nl | nw) atomic_add_u32(&sh.nlab, nl | (nw << 16));
     if (nf) atomic_add_u32(&sh.nfirst, nf);
     bk.sync();

@@ -28,11 +28,23 @@ fmt, rows, width, kind = {"libsvm": ("libsvm", 1 << 20, 128, synth.LIBSVM), "csv
                           # config 3's text with another delimiter / DType / label column (csv_fast.h WS, int label)
                           "csv_tsv": ("csv", 1 << 20, 256, synth.CSV), "csv_ssv": ("csv", 1 << 20, 256, synth.CSV),
                           "csv_i32_label0": ("csv", 1 << 20, 256, synth.CSV),
-                          "csv_tsv_label0": ("csv", 1 << 20, 256, synth.CSV)}[cfg]
+                          "csv_tsv_label0": ("csv", 1 << 20, 256, synth.CSV),
+                          # float label column over clean text, a header row, ", " separators, nan fields
+                          # (csv_fast.h TX: text, blanks and BOMs in the label / weight kernel)
+                          "csv_label0": ("csv", 1 << 20, 256, synth.CSV),
+                          "csv_hdr_label0": ("csv", 1 << 20, 256, synth.CSV),
+                          "csv_sp_label0": ("csv", 1 << 20, 256, synth.CSV_SP),
+                          "csv_nan_label0": ("csv", 1 << 20, 256, synth.CSV_NAN),
+                          "csv_hdr_label255": ("csv", 1 << 20, 256, synth.CSV)}[cfg]
 pkw = {"csv_tsv": {"delimiter": "\t"}, "csv_ssv": {"delimiter": " "},
        "csv_i32_label0": {"value_type": "i32", "label_column": 0},
-       "csv_tsv_label0": {"delimiter": "\t", "label_column": 0}}.get(cfg, {})
+       "csv_tsv_label0": {"delimiter": "\t", "label_column": 0},
+       "csv_label0": {"label_column": 0}, "csv_hdr_label0": {"label_column": 0}, "csv_sp_label0": {"label_column": 0},
+       "csv_nan_label0": {"label_column": 0}, "csv_hdr_label255": {"label_column": 255}}.get(cfg, {})
 text, _ = synth.rows(kind, rows, width, seed=1)
+if cfg.startswith("csv_hdr_label"):  # the header row of bench.py's csv_hdr_1m_x256
+    header = np.frombuffer((",".join("feature_%d" % j for j in range(width)) + "\n").encode(), np.uint8)
+    text = np.concatenate([header, text])
 if pkw.get("delimiter", ",") != ",":
     text = np.where(text == ord(","), np.uint8(ord(pkw["delimiter"])), text).astype(np.uint8)
 starts = dmlc_amd.text_chunk_starts(text)
