@@ -302,13 +302,20 @@ DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
   t.tlo = (uint64_t)k * kTile;
   t.thi = mn<uint64_t>(t.tlo + kTile, a.n);
   StageRegs sr;
+  // wave 0: the window of unit starts, issued ahead of the text loads so that
+  // the wait for it leaves them in flight (fast_common.h chunk_guess_begin)
+  ChunkProbe cp;
+  if (tid < kWave) cp = chunk_guess_begin(a.cs, a.nchunk, a.n, t.tlo, bk);
 #if defined(FSVM_GLDS) && defined(__HIP_DEVICE_COMPILE__)
-  stage_issue_lds(a.text, a.n, t.tlo, sr, sh.c, bk);  // text loads first: the chunk search overlaps them
+  constexpr bool kTextAfter = false;  // (the LDS-DMA form issues other loads: a full wait)
+  stage_issue_lds(a.text, a.n, t.tlo, sr, sh.c, bk);
 #else
-  stage_issue(a.text, a.n, t.tlo, sr, bk);  // text loads first: the chunk search overlaps them
+  constexpr bool kTextAfter = true;  // stage_issue's kStageRounds loads follow the window load
+  stage_issue(a.text, a.n, t.tlo, sr, bk);
 #endif
-  ChunkProbe cp;  // wave 0: the window load stays in flight through classification
-  if (tid < kWave) cp = chunk_list_begin(a.cs, a.nchunk, t.tlo, bk);
+  // the tile's chunk list, made in the shadow of the text loads; its readers
+  // come after the stage barrier
+  if (tid < kWave) chunk_guess_end(a.cs, a.nchunk, t.tlo, t.thi, cp, kTextAfter && sr.interior, sh.c, bk);
   if (tid == 0) {
     sh.u.m.d[0] = sh.u.m.n[0] = sh.u.m.l[0] = 0;
     sh.nlab = sh.nfirst = 0;
@@ -317,7 +324,7 @@ DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
   }
   for (int i = tid; i < kClsEntries; i += kFThreads)
     sh.cls[i] = class_of_csv((uint32_t)i, a.delim, !(SP && (WS || VT != 0)), JK, WS);
-  init_dec_tables(sh.dt, bk);
+  init_dec_tables(sh.dt, bk, kFThreads - kWave);  // the last wave: wave 0 makes the chunk list
   stage_commit(a.text, a.n, t.tlo, sr, sh.c, bk);
   bk.sync();
   // ---- classify: segment tid -> slot tid+1; lanes 0..15 also one dword
@@ -365,7 +372,6 @@ DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
       atomic_or_u64(&sh.u.m.l[0], (uint64_t)b.c << (4 * tid));
     }
   }
-  if (tid < kWave) chunk_list_end(a.cs, a.nchunk, t.tlo, t.thi, cp, sh.c, bk);
   bk.sync();
   if (tid == 0) bad |= sh.c.toomany;
   // ---- rows, fields, tokens of my segment

@@ -448,8 +448,9 @@ struct DecTables {
   uint64_t hib[9];          // 0x0F in bytes >= k of 8 (k <= 8): the fraction's byte masks
 };
 // The tables as compile-time constants (constant evaluation divides with
-// IEEE round-to-nearest, so i10[k] is the correctly rounded 10^-k); each tile
-// copies them to LDS with one load per lane instead of computing them.
+// IEEE round-to-nearest, so i10[k] is the correctly rounded 10^-k): what
+// init_dec_tables must produce, bit for bit (tests/emu/chunk_guess_check.cpp,
+// the decoders' goldens on the device).
 constexpr DecTables make_dec_tables() {
   DecTables t{};
   double p = 1.0;
@@ -466,14 +467,24 @@ constexpr DecTables make_dec_tables() {
   return t;
 }
 constexpr DecTables kDecTables = make_dec_tables();
+// Threads first .. first + 24 of the block fill the tile's copy in LDS, each
+// entry computed in registers: 10^t is an exact product of 10, 100, 1e4 and
+// 1e8 (t < 16: every partial product is below 2^53), 10^-t one IEEE f64
+// divide.  (Copied from kDecTables, each lane's global load was followed at
+// once by a full vmcnt(0) wait -- one more dependent trip to memory on the
+// tile prologue's path, which also drained every load issued before it.)
+// The single-pass tiles give the job to their last wave (first = its first
+// thread): wave 0 has the chunk list to make before the stage barrier.
 template <class BK>
-DA_HDF void init_dec_tables(DecTables &tb, BK &bk) {
-  const int t = bk.tid();
-  if (t < 16) {
-    tb.p10[t] = kDecTables.p10[t];
-    tb.i10[t] = kDecTables.i10[t];
-  } else if (t < 25) {
-    tb.hib[t - 16] = kDecTables.hib[t - 16];
+DA_HDF void init_dec_tables(DecTables &tb, BK &bk, int first = 0) {
+  const int t = bk.tid() - first;
+  if (t >= 0 && t < 16) {
+    const double p = pow10_exact((uint32_t)t);
+    tb.p10[t] = p;
+    tb.i10[t] = 1.0 / p;
+  } else if (t >= 16 && t < 25) {
+    const uint32_t k = (uint32_t)t - 16u;
+    tb.hib[k] = k >= 8u ? 0ull : 0x0F0F0F0F0F0F0F0Full << (8u * k);
   }
 }
 DA_HD uint32_t udot4(uint32_t a, uint32_t b, uint32_t c) {  // sum of the 4 byte products + c
@@ -661,9 +672,15 @@ struct TileCommon {
 // list comes from one more window load: csl = cs[c_first ..] inside [tlo, thi]
 // (excluding cs[nchunk]), cnext = the entry after the list (cs[nchunk] == n).
 //
-// Split in two so the last load's latency overlaps other prologue work:
-// chunk_list_begin runs the search rounds and issues the window load,
-// chunk_list_end consumes it (the caller classifies in between).
+// In two halves: chunk_list_begin runs the search rounds and issues the window
+// load, chunk_list_end consumes it.  The tile prologues first try the one
+// window a guess gives them (chunk_guess_begin / chunk_guess_end below) and
+// come here when it misses.
+
+// (the staged range in 16-byte units and load rounds: stage_issue below)
+constexpr int kStageUnits = kStage / 16;
+constexpr int kStageRounds = (kStageUnits + kFThreads - 1) / kFThreads;
+static_assert(kStage % 16 == 0, "staged range is whole 16-byte units");
 struct ChunkProbe {
   uint64_t lo, cnt, v;
 };
@@ -690,6 +707,35 @@ DA_HDF ChunkProbe chunk_list_begin(const uint64_t *cs, int nchunk, uint64_t tlo,
   p.v = lo + lane <= (uint64_t)nchunk ? cs[lo + lane] : kBig;
   return p;
 }
+// The list of the window v = cs[lo + lane] (beyond cs[nchunk]: kBig), where
+// cs[c0] is the chunk of tlo and c0 - lo <= kWave - kMaxCs - 2.  fits_only:
+// write nothing and return false when the tile holds more than kMaxCs starts
+// (toomany: the caller takes the search, whose window decides cnext then).
+template <class BK>
+DA_HDF bool chunk_list_write(int nchunk, uint64_t tlo, uint64_t thi, uint64_t lo, uint64_t v, uint64_t c0,
+                             bool fits_only, TileCommon &c, BK &bk) {
+  const uint32_t lane = (uint32_t)bk.tid();
+  const uint64_t kBig = ~0ull;
+  const uint64_t idx = lo + lane;
+  const uint64_t vf = bk.shfl(v, (int)(c0 - lo));  // cs[c0]
+  const uint32_t first = (uint32_t)(c0 - lo) + (vf < tlo ? 1u : 0u);  // lane of c_first
+  const uint64_t lm = bk.ballot(lane >= first && idx < (uint64_t)nchunk && v <= thi);
+  const uint32_t m_all = (uint32_t)popc64(lm);
+  const uint32_t ln = first + m_all;                                 // lane of cnext
+  const bool over = m_all > (uint32_t)kMaxCs || ln >= (uint32_t)kWave;
+  if (fits_only && over) return false;  // wave-uniform
+  const uint64_t vn = bk.shfl(v, (int)(ln < (uint32_t)kWave ? ln : 0u));
+  if (lane >= first && lane - first < (uint32_t)kMaxCs && ((lm >> lane) & 1u)) c.csl[lane - first] = v;
+  if (lane == 0) {
+    c.cfloor = vf;
+    c.c_first = (uint32_t)(lo + first);
+    c.ncs = over ? (uint32_t)kMaxCs : m_all;
+    c.cnext = ln < (uint32_t)kWave ? vn : kBig;
+    c.toomany = over;
+    c.bad = 0;
+  }
+  return true;
+}
 template <class BK>
 DA_HDF void chunk_list_end(const uint64_t *cs, int nchunk, uint64_t tlo, uint64_t thi, const ChunkProbe &p,
                            TileCommon &c, BK &bk) {
@@ -703,29 +749,99 @@ DA_HDF void chunk_list_end(const uint64_t *cs, int nchunk, uint64_t tlo, uint64_
     lo = c0;
     v = lo + lane <= (uint64_t)nchunk ? cs[lo + lane] : kBig;
   }
-  const uint64_t idx = lo + lane;
-  const uint64_t vf = bk.shfl(v, (int)(c0 - lo));  // cs[c0]
-  const uint32_t first = (uint32_t)(c0 - lo) + (vf < tlo ? 1u : 0u);  // lane of c_first
-  const uint64_t lm = bk.ballot(lane >= first && idx < (uint64_t)nchunk && v <= thi);
-  const uint32_t m_all = (uint32_t)popc64(lm);
-  const uint32_t ln = first + m_all;                                 // lane of cnext
-  const uint64_t vn = bk.shfl(v, (int)(ln < (uint32_t)kWave ? ln : 0u));
-  if (lane >= first && lane - first < (uint32_t)kMaxCs && ((lm >> lane) & 1u)) c.csl[lane - first] = v;
-  if (lane == 0) {
-    c.cfloor = vf;
-    c.c_first = (uint32_t)(lo + first);
-    const bool over = m_all > (uint32_t)kMaxCs || ln >= (uint32_t)kWave;
-    c.ncs = over ? (uint32_t)kMaxCs : m_all;
-    c.cnext = ln < (uint32_t)kWave ? vn : kBig;
-    c.toomany = over;
-    c.bad = 0;
-  }
+  (void)chunk_list_write(nchunk, tlo, thi, lo, v, c0, false, c, bk);
 }
+// The search form: one dependent trip to memory per factor of 64 chunks, one
+// for the window, one more when the list may run past it.
 template <class BK>
 DA_HDF void chunk_list(const uint64_t *cs, int nchunk, uint64_t tlo, uint64_t thi, TileCommon &c,
                        BK &bk) {
   const ChunkProbe p = chunk_list_begin(cs, nchunk, tlo, bk);
   chunk_list_end(cs, nchunk, tlo, thi, p, c, bk);
+}
+
+// The one-trip form the tile prologues use.  Unit starts are near-uniform in
+// real use -- InputSplit cuts equal buffers after their last newline, FillData
+// splits each evenly -- so the unit of tlo is close to tlo * nchunk / n.
+// chunk_guess_begin loads the one window of cs that puts that estimate
+// kGuessBack lanes in (the whole table when it fits a window); the caller
+// issues it BEFORE the tile's text loads, so that the wait for it is a
+// partial one (vector-memory returns count in order) with the text still in
+// flight.  chunk_guess_end makes the list from it when the window brackets
+// tlo low enough for the list to follow in it (chunk_list_end's condition)
+// and the tile holds at most kMaxCs starts; otherwise -- units far from
+// uniform, a found unit in the window's last lanes, toomany -- the search
+// above runs, so TileCommon is the search's for every input.
+//
+// The partial wait is spelled out.  The compiler places s_waitcnt from the
+// fewest loads any path puts after the one it waits for, and the paths that
+// stage no text (a tile at an end of the text) or skip a lane-guarded load
+// put fewer after the window load than wave 0 of an interior tile does: left
+// to it, the wait is vmcnt(0) -- the whole text fetch.  So on the device the
+// window load is an asm statement the compiler does not count, and
+// chunk_guess_end waits for it by hand: vmcnt(kStageRounds) when stage_issue
+// has put the text loads after it (text_in_flight: wave 0 executes each of
+// the kStageRounds load instructions -- its thread 0 owns a unit of every
+// round), vmcnt(0) otherwise.  More vector-memory instructions in between
+// than counted only make the wait stricter; the "memory" clobbers keep the
+// text loads between the two statements.
+constexpr int kGuessBack = (kWave - kMaxCs - 2) / 2;
+static_assert(kStageUnits > (kStageRounds - 1) * kFThreads, "thread 0 loads a unit in every stage round");
+template <class BK>
+DA_HDF ChunkProbe chunk_guess_begin(const uint64_t *cs, int nchunk, uint64_t n, uint64_t tlo, BK &bk) {
+  const uint32_t lane = (uint32_t)bk.tid();
+  uint64_t lo = 0;
+  if (nchunk >= kWave) {  // (else cs[0 .. nchunk] is one window)
+    // a float estimate: off by a 2^-22 of nchunk at most, far inside the window
+    const float g = (float)tlo * ((float)nchunk / (float)n);  // tlo < n: 0 <= g < 1.000001 nchunk
+    const uint32_t gi = mn<uint32_t>((uint32_t)g, (uint32_t)nchunk - 1u);
+    lo = gi > (uint32_t)kGuessBack ? gi - (uint32_t)kGuessBack : 0u;
+  }
+  ChunkProbe p;
+  p.lo = lo;
+  p.cnt = (uint64_t)kWave;
+  // (lanes past cs[nchunk] load it again; chunk_guess_end reads them as "beyond")
+  const uint64_t *src = cs + mn<uint64_t>(lo + lane, (uint64_t)nchunk);
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(p.v) : "v"(src) : "memory");
+#else
+  p.v = *src;
+#endif
+  return p;
+}
+template <class BK>
+DA_HDF void chunk_guess_end(const uint64_t *cs, int nchunk, uint64_t tlo, uint64_t thi, ChunkProbe &p,
+                            bool text_in_flight, TileCommon &c, BK &bk) {
+  const uint32_t lane = (uint32_t)bk.tid();
+#if defined(__HIP_DEVICE_COMPILE__)
+  // One statement for both waits, on p.v itself: until it has run, p.v is a
+  // register still being loaded that the compiler takes for written, so
+  // nothing may read or copy it first.  (Two statements, one per branch of an
+  // `if`, made the compiler join their results -- with a copy of p.v ahead of
+  // the wait on one side.)
+  asm volatile(
+      "s_cmp_eq_u32 %1, 0\n\t"
+      "s_cbranch_scc1 1f\n\t"
+      "s_waitcnt vmcnt(%2)\n\t"
+      "s_branch 2f\n"
+      "1:\n\t"
+      "s_waitcnt vmcnt(0)\n"
+      "2:"
+      : "+v"(p.v)
+      : "s"(__builtin_amdgcn_readfirstlane((uint32_t)text_in_flight)), "n"(kStageRounds)  // (wave-uniform)
+      : "scc", "memory");
+#else
+  (void)text_in_flight;
+#endif
+  uint64_t v = p.v;
+  if (p.lo + lane > (uint64_t)nchunk) v = ~0ull;
+  // lanes at or before the unit of tlo: a prefix of the window (cs ascends)
+  const uint64_t m = bk.ballot(p.lo + lane < (uint64_t)nchunk && v <= tlo);
+  const uint32_t top = 63u - (uint32_t)clz64(m | 1u);
+  bool done = false;
+  if ((m & 1u) && top <= (uint32_t)(kWave - kMaxCs - 2))  // wave-uniform
+    done = chunk_list_write(nchunk, tlo, thi, p.lo, v, p.lo + top, true, c, bk);
+  if (!done) chunk_list(cs, nchunk, tlo, thi, c, bk);
 }
 
 // All threads: stage [tlo - kPre, tlo + kTile + kPost) into LDS with 16-byte
@@ -766,9 +882,6 @@ DA_HDF void stage(const uint8_t *text, uint64_t n, uint64_t tlo, TileCommon &c, 
 // store waited for each load in turn: 5 HBM round trips per tile, ~14k cycles
 // of a ~57k-cycle tile.)  Tiles whose staged range leaves the text take the
 // byte-wise path of stage() at commit time.
-constexpr int kStageUnits = kStage / 16;
-constexpr int kStageRounds = (kStageUnits + kFThreads - 1) / kFThreads;
-static_assert(kStage % 16 == 0, "staged range is whole 16-byte units");
 struct StageRegs {
   uint32_t w[kStageRounds][4];
   bool interior;

@@ -1627,7 +1627,7 @@ DA_HDF uint32_t comments_reclassify(const Tile t, Shared &sh, uint32_t bad0, BK 
 template <class BK>
 DA_HDF void init_tables(Shared &sh, BK &bk) {
   for (int i = bk.tid(); i < kClsEntries; i += kFThreads) sh.cls[i] = class_of((uint32_t)i);
-  init_dec_tables(sh.dt, bk);
+  init_dec_tables(sh.dt, bk, kFThreads - kWave);  // the last wave: wave 0 makes the chunk list
 }
 
 // MODE 1: count only (size query); MODE 2: parse and write.
@@ -1671,10 +1671,16 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
   t.thi = mn<uint64_t>(t.tlo + kTile, a.n);
   uint32_t knext = a.ntiles;  // thread 0: the ticket's answer (PERSIST)
   if (PERSIST && tid == 0) knext = gridDim_x() + atomic_add_u32(a.ticket, 1u);
+  // wave 0: the window of unit starts, issued ahead of the text loads so that
+  // the wait for it leaves them in flight (fast_common.h chunk_guess_begin)
+  ChunkProbe cp;
+  if (tid < kWave) cp = chunk_guess_begin(a.cs, a.nchunk, a.n, t.tlo, bk);
 #if defined(FSVM_GLDS) && defined(__HIP_DEVICE_COMPILE__)
-  if (!PERSIST) stage_issue_lds(a.text, a.n, t.tlo, sr, sh.c, bk);  // text loads first: the chunk search overlaps them
+  constexpr bool kTextAfter = false;  // (the LDS-DMA form issues other loads: a full wait)
+  if (!PERSIST) stage_issue_lds(a.text, a.n, t.tlo, sr, sh.c, bk);
 #else
-  if (!PERSIST) stage_issue(a.text, a.n, t.tlo, sr, bk);  // text loads first: the chunk search overlaps them
+  constexpr bool kTextAfter = !PERSIST;  // stage_issue's kStageRounds loads follow the window load
+  if (!PERSIST) stage_issue(a.text, a.n, t.tlo, sr, bk);
 #endif
 #ifdef FSVM_PF_AHEAD  // A/B: touch tile k + FSVM_PF_AHEAD (same XCD) so its staging hits L2 / MALL
   uint32_t pfv = 0;
@@ -1683,8 +1689,9 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
     if (pk < a.ntiles && off < a.n) pfv = a.text[off];
   }
 #endif
-  ChunkProbe cp;  // wave 0: the window load stays in flight through classification
-  if (tid < kWave) cp = chunk_list_begin(a.cs, a.nchunk, t.tlo, bk);
+  // the tile's chunk list, made in the shadow of the text loads; its readers
+  // come after the stage barrier
+  if (tid < kWave) chunk_guess_end(a.cs, a.nchunk, t.tlo, t.thi, cp, kTextAfter && sr.interior, sh.c, bk);
   FAST_STAMP(k, 11);
   if (tid == 0) {
     sh.u.m.d[0] = sh.u.m.n[0] = sh.u.m.c[0] = 0;
@@ -1696,6 +1703,7 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
   }
   if (!PERSIST) init_tables(sh, bk);
   stage_commit(a.text, a.n, t.tlo, sr, sh.c, bk);
+  FAST_STAMP(k, 10);  // wave 0 is at the stage barrier: its own text has landed and is stored
   bk.sync();
   FAST_STAMP(k, 2);
 #if defined(FSVM_ABL_STOP) && FSVM_ABL_STOP == 0  // timing ablation only: stage
@@ -1712,8 +1720,6 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
   };
   uint32_t bad = classify_tile<FM>(t, sh, tid, at, true, 7u);
   FAST_STAMP(k, 9);
-  if (tid < kWave) chunk_list_end(a.cs, a.nchunk, t.tlo, t.thi, cp, sh.c, bk);
-  FAST_STAMP(k, 10);
   bk.sync();
   // a byte outside the grammar ('#' among them) in the tile or in the pre-halo:
   // blank the comments and classify again (block-uniform, libsvm only)

@@ -63,9 +63,11 @@ def main():
             print("  %-14s mean %8.0f cyc  p50 %8.0f  p99 %8.0f" % (PHASES[i], col.mean(), np.median(col),
                                                                    np.percentile(col, 99)))
         print("  total          mean %8.0f cyc" % d.sum(axis=1).mean())
-        if mode == "full":  # sub-phases (thread 0): stage issue / wait; classify compute / chunk list / barrier
-            for name, a0, a1 in (("  stage issue", 1, 11), ("  stage wait+sync", 11, 2), ("  classify body", 2, 9),
-                                 ("  chunk list end", 9, 10), ("  classify barrier", 10, 3)):
+        if mode == "full":  # sub-phases (thread 0, wave 0): the stage phase up to the chunk list written (window
+            # load, text loads issued, partial wait, list), then to wave 0's own text stored, then its wait at
+            # the stage barrier for waves 1-3; classify compute / barrier
+            for name, a0, a1 in (("  issue+chunk list", 1, 11), ("  own text+commit", 11, 10), ("  stage barrier", 10, 2),
+                                 ("  classify body", 2, 9), ("  classify barrier", 9, 3)):
                 col = st[:, a1] - st[:, a0]
                 print("  %-18s mean %8.0f cyc  p50 %8.0f" % (name, col.mean(), np.median(col)))
         if mode == "full":  # the slowest tiles (e.g. the comment / dirty-line pass) and their successors' wait
@@ -74,7 +76,7 @@ def main():
             print("  slowest classify (tile: cycles): %s" % ", ".join("%d: %d" % (k, cls[k]) for k in top))
             hz = st[:, 12] > st[:, 2]  # tiles that took the comment / dirty-line pass this run
             if hz.any():
-                for name, a0, a1 in (("comment pass", 2, 12), ("  erase", 10, 16), ("    masks+prehalo", 10, 17),
+                for name, a0, a1 in (("comment pass", 2, 12), ("  erase", 9, 16), ("    masks+prehalo", 9, 17),
                                      ("    scan 1", 17, 18), ("    scan 2", 18, 19), ("    blank+sync", 19, 16),
                                      ("  reclassify", 16, 12),
                                      ("dirty: walk", 12, 13), ("dirty: rest", 13, 14)):
