@@ -414,6 +414,57 @@ int dmlc_amd_parse(const void *d_text, uint64_t nbytes, const uint64_t *d_chunk_
   return e == hipSuccess ? DMLC_AMD_OK : DMLC_AMD_ERR_HIP;
 }
 
+int dmlc_amd_dense_geometry(uint32_t *cells_per_tile, uint32_t *rows_per_tile) {
+  if (cells_per_tile) *cells_per_tile = dmlc_amd::kDenseCells;
+  if (rows_per_tile) *rows_per_tile = dmlc_amd::kDenseRows;
+  return DMLC_AMD_OK;
+}
+
+int dmlc_amd_to_dense(const dmlc_amd_csr *csr, const dmlc_amd_result *d_result,
+                      const dmlc_amd_dense_params *prm, void *d_out, uint64_t *d_status, void *stream) {
+  if (!csr || !d_result || !prm || !d_out || !d_status) return DMLC_AMD_ERR_ARG;
+  if (prm->index_bits != 32 && prm->index_bits != 64) return DMLC_AMD_ERR_ARG;
+  if (prm->value_type < DMLC_AMD_F32 || prm->value_type > DMLC_AMD_I64) return DMLC_AMD_ERR_ARG;
+  if (prm->ncol == 0 || prm->ld < prm->ncol) return DMLC_AMD_ERR_ARG;
+  const int vbytes = prm->value_type == DMLC_AMD_I64 ? 8 : 4;
+  if (reinterpret_cast<uintptr_t>(d_out) % (uintptr_t)vbytes) return DMLC_AMD_ERR_ARG;
+  // the rows the window can hold: the parsed count is known on the device
+  // only, so tiles are launched for all of them and leave early past it
+  const uint64_t cap_rows = csr->cap[DMLC_AMD_ROWS];
+  const uint64_t nrows = prm->row_begin < cap_rows ? dmlc_amd::mn<uint64_t>(prm->max_rows, cap_rows - prm->row_begin) : 0;
+  if (nrows && (!csr->offset || (csr->cap[DMLC_AMD_INDEX] && !csr->index))) return DMLC_AMD_ERR_ARG;
+  dmlc_amd::DenseArgs a;
+  std::memset(&a, 0, sizeof(a));
+  dmlc_amd::dense_shape(prm->ncol, &a.S, &a.R);
+  const uint64_t col_tiles = (prm->ncol - 1) / a.S + 1;
+  const uint64_t row_tiles = nrows ? (nrows - 1) / a.R + 1 : 0;
+  // never truncated: a window of more tiles than the grid holds is refused
+  if (col_tiles > dmlc_amd::kDenseMaxTiles || row_tiles > dmlc_amd::kDenseMaxTiles ||
+      col_tiles * row_tiles > dmlc_amd::kDenseMaxTiles)
+    return DMLC_AMD_ERR_ARG;
+  a.offset = csr->offset;
+  a.index = csr->index;
+  a.value = csr->value;
+  a.res = reinterpret_cast<const uint64_t *>(d_result);
+  a.cap_rows = cap_rows;
+  a.cap_index = csr->cap[DMLC_AMD_INDEX];
+  // (without a value array the kernel reads none: count[VALUE] == 0 gives ones)
+  a.cap_value = csr->value ? csr->cap[DMLC_AMD_VALUE] : 0;
+  a.row_begin = prm->row_begin;
+  a.row_end = prm->row_begin + prm->max_rows < prm->row_begin ? ~0ull : prm->row_begin + prm->max_rows;
+  a.ncol = prm->ncol;
+  a.ld = prm->ld;
+  a.fill = vbytes == 8 ? prm->fill_bits : (prm->fill_bits & 0xFFFFFFFFull);
+  a.one = prm->value_type == DMLC_AMD_F32 ? 0x3F800000ull : 1ull;
+  a.col_tiles = (uint32_t)col_tiles;
+  a.out = d_out;
+  a.status = d_status;
+  const hipError_t e = dmlc_amd::launch_dense(a, prm->index_bits == 64, vbytes, (uint32_t)(col_tiles * row_tiles),
+                                              reinterpret_cast<hipStream_t>(stream));
+  g_last_hip = e;
+  return e == hipSuccess ? DMLC_AMD_OK : DMLC_AMD_ERR_HIP;
+}
+
 const char *dmlc_amd_last_hip_error(void) { return hipGetErrorString(g_last_hip); }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "args.h"
+#include "dense_core.h"
 
 namespace dmlc_amd {
 
@@ -34,5 +35,8 @@ hipError_t launch_max(const void *arr, int wide, const uint64_t *count, uint64_t
                       hipStream_t s);
 hipError_t launch_csv(const CsvArgs &a, const FastCsvArgs &f, bool use_fast, uint64_t *res, int phase,
                       hipStream_t s);
+// CSR -> dense row batch (dense_core.h): d_status, then ntiles tiles (0 = d_status only);
+// indices are u32, or u64 when wide; values are 4- or 8-byte bit patterns
+hipError_t launch_dense(const DenseArgs &a, int wide, int value_bytes, uint32_t ntiles, hipStream_t s);
 
 }  // namespace dmlc_amd

@@ -71,6 +71,18 @@ DA_HD void atomic_max_u64(unsigned long long *p, unsigned long long v) {
 #endif
 }
 
+// 32-bit max with no value returned: on an LDS word it is one ds_max_u32
+// (dense_core.h's cell tags)
+DA_HD void atomic_max_u32(uint32_t *p, uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  atomicMax(p, v);
+#else
+  uint32_t cur = __atomic_load_n(p, __ATOMIC_RELAXED);
+  while (v > cur && !__atomic_compare_exchange_n(p, &cur, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {
+  }
+#endif
+}
+
 // atomic min, skipped when a plain read already shows a value <= v: minima
 // of many tiles on one word (a ParseBlock unit's) mostly do not improve it,
 // and same-address device atomics serialise (a stale read only costs an

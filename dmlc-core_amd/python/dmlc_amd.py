@@ -39,6 +39,18 @@ class Csr(ctypes.Structure):
                 ("value", ctypes.c_void_p), ("cap", ctypes.c_uint64 * 8)]
 
 
+class DenseParams(ctypes.Structure):
+    """dmlc_amd_dense_params (64 bytes)."""
+    _fields_ = [("index_bits", ctypes.c_int32), ("value_type", ctypes.c_int32),
+                ("row_begin", ctypes.c_uint64), ("max_rows", ctypes.c_uint64), ("ncol", ctypes.c_uint64),
+                ("ld", ctypes.c_uint64), ("fill_bits", ctypes.c_uint64),
+                ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
+# d_status words of dmlc_amd_to_dense and its flag bits
+DENSE_ROWS, DENSE_DROPPED, DENSE_FIRST, DENSE_FLAGS = range(4)
+DENSE_FLAG_ERROR, DENSE_FLAG_VALUE_COUNT, DENSE_FLAG_OFFSET_CAP, DENSE_FLAG_ROW_TOO_LONG = 1, 2, 4, 8
+
 _LIB = None
 
 
@@ -83,6 +95,12 @@ def lib():
         if hasattr(L, "dmlc_amd_fast_geometry"):  # (A/B builds of older sources lack it)
             L.dmlc_amd_fast_geometry.restype = ctypes.c_int
             L.dmlc_amd_fast_geometry.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
+        if hasattr(L, "dmlc_amd_to_dense"):  # (A/B builds of older sources lack it)
+            L.dmlc_amd_to_dense.restype = ctypes.c_int
+            L.dmlc_amd_to_dense.argtypes = [ctypes.POINTER(Csr), ctypes.c_void_p, ctypes.POINTER(DenseParams),
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+            L.dmlc_amd_dense_geometry.restype = ctypes.c_int
+            L.dmlc_amd_dense_geometry.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
         L.dmlc_amd_profile_begin.restype = ctypes.c_int
         L.dmlc_amd_profile_end.restype = ctypes.c_int
         L.dmlc_amd_profile_end.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int),
@@ -107,7 +125,27 @@ EXPORTED_SYMBOLS = ("dmlc_amd_parse", "dmlc_amd_workspace_bytes", "dmlc_amd_erro
                     "dmlc_amd_device_count", "dmlc_amd_abi_version", "dmlc_amd_strtof_batch",
                     "dmlc_amd_profile_begin", "dmlc_amd_profile_end", "dmlc_amd_last_hip_error",
                     "dmlc_amd_copy", "dmlc_amd_copy_n", "dmlc_amd_copy_n_dev", "dmlc_amd_fast_geometry",
-                    "dmlc_amd_build_id")
+                    "dmlc_amd_build_id", "dmlc_amd_to_dense", "dmlc_amd_dense_geometry")
+
+
+def dense_geometry():
+    """(cells per tile, most rows per tile) of dmlc_amd_to_dense in the loaded
+    library: a workgroup owns S = min(ncol, cells) columns of min(rows, cells
+    // S) rows (dmlc_amd_dense_geometry)."""
+    c, r = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    lib().dmlc_amd_dense_geometry(ctypes.byref(c), ctypes.byref(r))
+    return int(c.value), int(r.value)
+
+
+def fill_bits_of(fill, value_type):
+    """Bit pattern of `fill` as the value type (F32 | I32 | I64)."""
+    if value_type == F32:
+        return int(np.array([fill], dtype=np.float32).view(np.uint32)[0])
+    if isinstance(fill, float) and fill != fill:
+        raise ValueError("an integer value type has no NaN: pass fill= or fill_bits=")
+    if value_type == I32:
+        return int(np.array([fill], dtype=np.int32).view(np.uint32)[0])
+    return int(np.array([fill], dtype=np.int64).view(np.uint64)[0])
 
 
 def fast_geometry():
@@ -258,6 +296,98 @@ class DeviceParser:
         out["path"] = int(r[9])
         out["result_counts"] = [int(x) for x in r[:8]]
         out["max_index"], out["max_field"] = int(r[10]), int(r[11])
+        out["result"] = res  # the device result block (to_dense reads its counts)
+        return out
+
+    # ---- dense row batches (dmlc_amd_to_dense)
+    def _value_type(self):
+        return self.params.value_type if self.params.format == CSV else F32
+
+    def to_dense_async(self, out, result, dense, *, ncol, row_begin=0, max_rows=None, fill=float("nan"),
+                       fill_bits=None, status=None, stream=None):
+        """Launch the CSR -> dense pass behind the parse that fills `result`
+        (same stream, no host sync): rows [row_begin, row_begin + max_rows) of
+        the parsed batch `out` into `dense`, a 2-D device tensor of the value
+        dtype with ncol columns (a strided view is fine: ld = dense.stride(0)).
+        max_rows defaults to dense.shape[0]; rows the parse did not produce
+        stay unwritten.  `fill` goes into cells without an entry, by value or
+        as an explicit bit pattern `fill_bits`.  Returns the device status
+        tensor (int64[4]: rows written, entries dropped, first dropped
+        position, DENSE_FLAG_* bits)."""
+        torch = self.torch
+        vt = self._value_type()
+        if dense.dim() != 2 or int(dense.shape[1]) != int(ncol) or dense.dtype != _vdt(torch, vt):
+            raise ValueError("dense must be a 2-D %s tensor with ncol = %d columns" % (_vdt(torch, vt), ncol))
+        if int(ncol) > 1 and dense.stride(1) != 1:
+            raise ValueError("dense rows must be contiguous (stride(1) == 1)")
+        nrow = int(dense.shape[0])
+        if max_rows is None:
+            max_rows = nrow
+        if max_rows > nrow:
+            raise ValueError("max_rows = %d exceeds the %d rows of dense" % (max_rows, nrow))
+        if status is None:
+            status = torch.empty(4, dtype=torch.int64, device=dense.device)
+        p = DenseParams()
+        p.index_bits = self.params.index_bits
+        p.value_type = vt
+        p.row_begin, p.max_rows, p.ncol = int(row_begin), int(max_rows), int(ncol)
+        p.ld = max(int(dense.stride(0)), int(ncol)) if nrow > 1 else int(ncol)
+        p.fill_bits = int(fill_bits) if fill_bits is not None else fill_bits_of(fill, vt)
+        csr = out.get("_csr") or self.csr_of(out)
+        s = stream if stream is not None else torch.cuda.current_stream()
+        # (an empty tensor has no storage: max_rows == 0 only sets the status, any non-null pointer does)
+        rc = lib().dmlc_amd_to_dense(ctypes.byref(csr), result.data_ptr(), ctypes.byref(p),
+                                     dense.data_ptr() if nrow else status.data_ptr(), status.data_ptr(),
+                                     s.cuda_stream)
+        if rc != 0:
+            msg = lib().dmlc_amd_error_string(rc).decode()
+            if rc == 33:
+                msg += " (%s)" % lib().dmlc_amd_last_hip_error().decode()
+            raise RuntimeError("dmlc_amd_to_dense: %s" % msg)
+        return status
+
+    def to_dense(self, out, ncol=None, fill=float("nan"), row_begin=0, max_rows=None, fill_bits=None):
+        """Dense rows of a batch returned by parse(): (tensor, status) after a
+        sync, status as uint64[4].  ncol=None means max_index + 1 (the NumCol
+        of the reference's BasicRowIter), which needs a parser made with
+        flags=FLAG_MAX_INDEX."""
+        torch = self.torch
+        if ncol is None:
+            if not self.params.flags & FLAG_MAX_INDEX:
+                raise ValueError("ncol=None needs a parse made with FLAG_MAX_INDEX (result.max_index)")
+            ncol = int(out["max_index"]) + 1
+        rows = int(out["counts"][ROWS])
+        if max_rows is None:
+            max_rows = max(rows - int(row_begin), 0)
+        dense = torch.empty((int(max_rows), int(ncol)), dtype=_vdt(torch, self._value_type()), device="cuda")
+        status = self.to_dense_async(out, out["result"], dense, ncol=ncol, row_begin=row_begin,
+                                     max_rows=max_rows, fill=fill, fill_bits=fill_bits)
+        return dense, status.cpu().numpy().view(np.uint64)
+
+    def parse_dense(self, text, chunk_starts, ncol, fill=float("nan"), fill_bits=None, stream=None):
+        """Text -> dense rows: count, allocate, then the write pass and the
+        dense pass on one stream with no host sync between the two.  Returns
+        parse()'s dict with "dense" (rows x ncol) and "dense_status"."""
+        torch = self.torch
+        res = torch.zeros(16, dtype=torch.int64, device="cuda")
+        counts = self.count(text, chunk_starts, stream, result=res)
+        out = self.alloc(counts)
+        nchunks = int(chunk_starts.numel()) - 1
+        out["chunk_table"] = torch.zeros(max(nchunks * units_per_chunk(self.params), 1) * 8, dtype=torch.int64,
+                                         device="cuda")
+        dense = torch.empty((int(counts[ROWS]), int(ncol)), dtype=_vdt(torch, self._value_type()), device="cuda")
+        self.fill_async(text, chunk_starts, out, res, chunk_table=out["chunk_table"] if nchunks > 0 else None,
+                        stream=stream)
+        status = self.to_dense_async(out, res, dense, ncol=ncol, fill=fill, fill_bits=fill_bits, stream=stream)
+        if stream is not None:
+            stream.synchronize()
+        r = res.cpu().numpy().view(np.uint64)
+        out["error"], out["path"] = int(r[8]), int(r[9])
+        out["result_counts"] = [int(x) for x in r[:8]]
+        out["max_index"], out["max_field"] = int(r[10]), int(r[11])
+        out["result"] = res
+        out["dense"] = dense
+        out["dense_status"] = status.cpu().numpy().view(np.uint64)
         return out
 
 

@@ -133,6 +133,61 @@ int dmlc_amd_parse(const void *d_text, uint64_t nbytes, const uint64_t *d_chunk_
                    void *d_workspace, size_t workspace_bytes, dmlc_amd_result *d_result,
                    void *stream);
 
+/* Dense row batch from a parsed CSR: the rows [row_begin, row_begin +
+ * max_rows) that the parse produced, as a row-major matrix of ncol columns and
+ * leading dimension ld >= ncol (in elements) at d_out, element type = the
+ * value type.  With rows = min(result.count[ROWS], csr.cap[ROWS]):
+ *
+ *   for r in row_begin .. min(rows, row_begin + max_rows) - 1:
+ *     out[(r - row_begin) * ld + 0 .. ncol-1] = fill
+ *     for k in offset[r] .. offset[r+1]-1, ascending:
+ *       c = index[k]                            (compared as 64-bit)
+ *       if c < ncol: out[(r - row_begin) * ld + c] = count[VALUE] == 0 ? 1 : value[k]
+ *       else:        dropped += 1; first_dropped = min(first_dropped, k)
+ *
+ * A later entry of the same row and column overwrites an earlier one (the last
+ * wins, deterministically).  No value array means 1 (RowBlock::get_value,
+ * include/dmlc/data.h).  Values are copied bit for bit.  Elements between ncol
+ * and ld, and rows of d_out past the parsed row count, are never written;
+ * d_out is never read.  fill_bits is the fill's bit pattern (its low 32 bits
+ * for the 4-byte types).  libfm's field array is ignored. */
+typedef struct dmlc_amd_dense_params {
+  int32_t index_bits; /* 32 | 64 */
+  int32_t value_type; /* DMLC_AMD_F32 | I32 | I64 */
+  uint64_t row_begin, max_rows, ncol, ld, fill_bits;
+  uint32_t flags, reserved[3]; /* 0 */
+} dmlc_amd_dense_params;
+
+/* d_status: uint64_t[4] in device memory, set by the call itself */
+enum {
+  DMLC_AMD_DENSE_ROWS = 0,    /* rows written (0 with flag bits 0 / 1) */
+  DMLC_AMD_DENSE_DROPPED = 1, /* entries dropped because index >= ncol */
+  DMLC_AMD_DENSE_FIRST = 2,   /* smallest position k of a dropped entry, ~0 if none */
+  DMLC_AMD_DENSE_FLAGS = 3    /* DMLC_AMD_DENSE_FLAG_* */
+};
+#define DMLC_AMD_DENSE_FLAG_ERROR 1u       /* result.error != 0: nothing is written */
+#define DMLC_AMD_DENSE_FLAG_VALUE_COUNT 2u /* count[VALUE] is neither 0 nor count[INDEX] (GetBlock's
+                                              CHECK, row_block.h:171-189): nothing is written */
+#define DMLC_AMD_DENSE_FLAG_OFFSET_CAP 4u  /* an offset pointed past the index (or value) capacity: no
+                                              element at or past it is read, such entries are skipped */
+#define DMLC_AMD_DENSE_FLAG_ROW_TOO_LONG 8u /* a row of 2^32 - 1 or more entries: its tile of rows is not
+                                               written, the matrix is not valid */
+
+/* Asynchronous on `stream`, after the parse that fills *d_result; no host
+ * synchronisation, allocation or device-wide barrier.  csr->cap bounds every
+ * read.  Returns DMLC_AMD_ERR_ARG before any HIP call for a null pointer,
+ * ncol == 0, ld < ncol, bad index_bits / value_type, d_out not aligned to its
+ * element, or a window of more tiles than one launch holds (2^31 - 1; see
+ * dmlc_amd_dense_geometry -- split the rows over several calls).  max_rows ==
+ * 0 only sets d_status. */
+int dmlc_amd_to_dense(const dmlc_amd_csr *csr, const dmlc_amd_result *d_result,
+                      const dmlc_amd_dense_params *prm, void *d_out, uint64_t *d_status, void *stream);
+
+/* Tile geometry this library was built with: a workgroup owns S = min(ncol,
+ * cells_per_tile) columns of R = min(rows_per_tile, cells_per_tile / S) rows
+ * (either pointer may be NULL). */
+int dmlc_amd_dense_geometry(uint32_t *cells_per_tile, uint32_t *rows_per_tile);
+
 /* Batch dmlc::strtof (ParseFloat<float>, strtonum.h:95-264, :279-281): string i
  * is d_text[d_offsets[i] .. d_offsets[i+1]) read as NUL-terminated at its end.
  * Writes the value, the bytes consumed (endptr - nptr) and the "Invalid NAN
