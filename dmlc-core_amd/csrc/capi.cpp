@@ -465,6 +465,89 @@ int dmlc_amd_to_dense(const dmlc_amd_csr *csr, const dmlc_amd_result *d_result,
   return e == hipSuccess ? DMLC_AMD_OK : DMLC_AMD_ERR_HIP;
 }
 
+int dmlc_amd_gather_geometry(uint32_t *rows_per_tile) {
+  if (rows_per_tile) *rows_per_tile = dmlc_amd::kGatherRows;
+  return DMLC_AMD_OK;
+}
+
+// one record per tile of ids (gather_core.h), in whole 256-byte lines
+size_t dmlc_amd_gather_workspace_bytes(uint64_t n_ids) {
+  const uint64_t ntiles = n_ids / dmlc_amd::kGatherRows + (n_ids % dmlc_amd::kGatherRows != 0);
+  return (size_t)(((ntiles * dmlc_amd::kGatherRecWords * sizeof(uint64_t) + 255) & ~255ull) + 256);
+}
+
+namespace {
+// the arrays of one side as the kernels take them: a null array holds nothing
+dmlc_amd::GatherCsr gather_side(const dmlc_amd_csr *c) {
+  dmlc_amd::GatherCsr g;
+  std::memset(&g, 0, sizeof(g));
+  g.offset = c->offset;
+  g.label = c->label;
+  g.weight = reinterpret_cast<uint32_t *>(c->weight);
+  g.qid = c->qid;
+  g.field = c->field;
+  g.index = c->index;
+  g.value = c->value;
+  g.cap[DMLC_AMD_ROWS] = c->offset ? c->cap[DMLC_AMD_ROWS] : 0;
+  g.cap[DMLC_AMD_LABEL] = c->label ? g.cap[DMLC_AMD_ROWS] : 0;  // cap[ROWS] counts labels
+  g.cap[DMLC_AMD_WEIGHT] = c->weight ? c->cap[DMLC_AMD_WEIGHT] : 0;
+  g.cap[DMLC_AMD_QID] = c->qid ? c->cap[DMLC_AMD_QID] : 0;
+  g.cap[DMLC_AMD_INDEX] = c->index ? c->cap[DMLC_AMD_INDEX] : 0;
+  g.cap[DMLC_AMD_VALUE] = c->value ? c->cap[DMLC_AMD_VALUE] : 0;
+  g.cap[DMLC_AMD_FIELD] = c->field ? c->cap[DMLC_AMD_FIELD] : 0;
+  return g;
+}
+bool same_array(const void *a, const void *b) { return a != nullptr && a == b; }
+}  // namespace
+
+int dmlc_amd_gather_rows(const dmlc_amd_csr *src, const dmlc_amd_result *d_src_result, const void *d_ids,
+                         uint64_t n_ids, const dmlc_amd_gather_params *prm, const dmlc_amd_csr *dst,
+                         dmlc_amd_result *d_dst_result, uint64_t *d_status, void *d_workspace,
+                         size_t workspace_bytes, void *stream) {
+  if (!src || !d_src_result || !prm || !dst || !d_dst_result || !d_status || !d_workspace) return DMLC_AMD_ERR_ARG;
+  if (n_ids && !d_ids) return DMLC_AMD_ERR_ARG;
+  if (!dst->offset) return DMLC_AMD_ERR_ARG;  // dst.offset[0] is always written
+  if (prm->index_bits != 32 && prm->index_bits != 64) return DMLC_AMD_ERR_ARG;
+  if (prm->id_bits != 32 && prm->id_bits != 64) return DMLC_AMD_ERR_ARG;
+  if (prm->value_type < DMLC_AMD_F32 || prm->value_type > DMLC_AMD_I64) return DMLC_AMD_ERR_ARG;
+  if (prm->label_type < DMLC_AMD_F32 || prm->label_type > DMLC_AMD_I64) return DMLC_AMD_ERR_ARG;
+  if (prm->flags & ~DMLC_AMD_FLAG_MAX_INDEX) return DMLC_AMD_ERR_ARG;
+  if (prm->reserved[0] || prm->reserved[1] || prm->reserved[2]) return DMLC_AMD_ERR_ARG;
+  const uint64_t ntiles = n_ids / dmlc_amd::kGatherRows + (n_ids % dmlc_amd::kGatherRows != 0);
+  // never truncated: more ids than the grid holds tiles for are refused
+  if (ntiles > dmlc_amd::kGatherMaxTiles) return DMLC_AMD_ERR_ARG;
+  if (workspace_bytes < dmlc_amd_gather_workspace_bytes(n_ids)) return DMLC_AMD_ERR_ARG;
+  if (same_array(src->offset, dst->offset) || same_array(src->label, dst->label) ||
+      same_array(src->weight, dst->weight) || same_array(src->qid, dst->qid) || same_array(src->field, dst->field) ||
+      same_array(src->index, dst->index) || same_array(src->value, dst->value) ||
+      same_array(d_src_result, d_dst_result))
+    return DMLC_AMD_ERR_ARG;
+  dmlc_amd::GatherArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.src = gather_side(src);
+  a.dst = gather_side(dst);
+  a.res = reinterpret_cast<const uint64_t *>(d_src_result);
+  a.dres = reinterpret_cast<uint64_t *>(d_dst_result);
+  a.ids = d_ids;
+  a.n_ids = n_ids;
+  a.ntiles = ntiles;
+  a.id_wide = prm->id_bits == 64;
+  a.label_bytes = prm->label_type == DMLC_AMD_I64 ? 8 : 4;
+  a.rec = reinterpret_cast<uint64_t *>(d_workspace);
+  a.status = d_status;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int wide = prm->index_bits == 64;
+  hipError_t e = dmlc_amd::launch_gather(a, wide, prm->value_type == DMLC_AMD_I64 ? 8 : 4, s);
+  if (e == hipSuccess && (prm->flags & DMLC_AMD_FLAG_MAX_INDEX)) {
+    // maxima of what was written, as after a parse
+    e = dmlc_amd::launch_max(a.dst.index, wide, a.dres + DMLC_AMD_INDEX, a.dst.cap[DMLC_AMD_INDEX], a.dres + 10, s);
+    if (e == hipSuccess)
+      e = dmlc_amd::launch_max(a.dst.field, wide, a.dres + DMLC_AMD_FIELD, a.dst.cap[DMLC_AMD_FIELD], a.dres + 11, s);
+  }
+  g_last_hip = e;
+  return e == hipSuccess ? DMLC_AMD_OK : DMLC_AMD_ERR_HIP;
+}
+
 const char *dmlc_amd_last_hip_error(void) { return hipGetErrorString(g_last_hip); }
 
 }  // extern "C"

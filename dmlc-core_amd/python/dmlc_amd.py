@@ -47,6 +47,16 @@ class DenseParams(ctypes.Structure):
                 ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
 
 
+class GatherParams(ctypes.Structure):
+    """dmlc_amd_gather_params (32 bytes)."""
+    _fields_ = [("index_bits", ctypes.c_int32), ("value_type", ctypes.c_int32), ("label_type", ctypes.c_int32),
+                ("id_bits", ctypes.c_int32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
+# d_status words of dmlc_amd_gather_rows and its flag bits
+GATHER_ROWS, GATHER_BAD, GATHER_FIRST, GATHER_FLAGS = range(4)
+GATHER_FLAG_ERROR, GATHER_FLAG_COUNT, GATHER_FLAG_OFFSET_CAP, GATHER_FLAG_CAPACITY = 1, 2, 4, 8
+
 # d_status words of dmlc_amd_to_dense and its flag bits
 DENSE_ROWS, DENSE_DROPPED, DENSE_FIRST, DENSE_FLAGS = range(4)
 DENSE_FLAG_ERROR, DENSE_FLAG_VALUE_COUNT, DENSE_FLAG_OFFSET_CAP, DENSE_FLAG_ROW_TOO_LONG = 1, 2, 4, 8
@@ -101,6 +111,15 @@ def lib():
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
             L.dmlc_amd_dense_geometry.restype = ctypes.c_int
             L.dmlc_amd_dense_geometry.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
+        if hasattr(L, "dmlc_amd_gather_rows"):  # (A/B builds of older sources lack it)
+            L.dmlc_amd_gather_workspace_bytes.restype = ctypes.c_size_t
+            L.dmlc_amd_gather_workspace_bytes.argtypes = [ctypes.c_uint64]
+            L.dmlc_amd_gather_rows.restype = ctypes.c_int
+            L.dmlc_amd_gather_rows.argtypes = [ctypes.POINTER(Csr), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                               ctypes.POINTER(GatherParams), ctypes.POINTER(Csr), ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+            L.dmlc_amd_gather_geometry.restype = ctypes.c_int
+            L.dmlc_amd_gather_geometry.argtypes = [ctypes.POINTER(ctypes.c_uint32)]
         L.dmlc_amd_profile_begin.restype = ctypes.c_int
         L.dmlc_amd_profile_end.restype = ctypes.c_int
         L.dmlc_amd_profile_end.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int),
@@ -125,7 +144,8 @@ EXPORTED_SYMBOLS = ("dmlc_amd_parse", "dmlc_amd_workspace_bytes", "dmlc_amd_erro
                     "dmlc_amd_device_count", "dmlc_amd_abi_version", "dmlc_amd_strtof_batch",
                     "dmlc_amd_profile_begin", "dmlc_amd_profile_end", "dmlc_amd_last_hip_error",
                     "dmlc_amd_copy", "dmlc_amd_copy_n", "dmlc_amd_copy_n_dev", "dmlc_amd_fast_geometry",
-                    "dmlc_amd_build_id", "dmlc_amd_to_dense", "dmlc_amd_dense_geometry")
+                    "dmlc_amd_build_id", "dmlc_amd_to_dense", "dmlc_amd_dense_geometry", "dmlc_amd_gather_rows",
+                    "dmlc_amd_gather_workspace_bytes", "dmlc_amd_gather_geometry")
 
 
 def dense_geometry():
@@ -135,6 +155,14 @@ def dense_geometry():
     c, r = ctypes.c_uint32(0), ctypes.c_uint32(0)
     lib().dmlc_amd_dense_geometry(ctypes.byref(c), ctypes.byref(r))
     return int(c.value), int(r.value)
+
+
+def gather_geometry():
+    """Ids per tile (one workgroup) of dmlc_amd_gather_rows in the loaded
+    library (dmlc_amd_gather_geometry)."""
+    r = ctypes.c_uint32(0)
+    lib().dmlc_amd_gather_geometry(ctypes.byref(r))
+    return int(r.value)
 
 
 def fill_bits_of(fill, value_type):
@@ -198,6 +226,7 @@ class DeviceParser:
         self.params = make_params(fmt, **kw)
         self.torch = _torch()
         self._ws = None
+        self._gws = None  # gather_rows_async's workspace
 
     def _workspace(self, nbytes, nchunks):
         need = lib().dmlc_amd_workspace_bytes(nbytes, nchunks, ctypes.byref(self.params))
@@ -389,6 +418,96 @@ class DeviceParser:
         out["dense"] = dense
         out["dense_status"] = status.cpu().numpy().view(np.uint64)
         return out
+
+    # ---- row gather: shuffle / select rows of a parsed batch (dmlc_amd_gather_rows)
+    def gather_rows_async(self, out, result, ids, dst=None, dst_result=None, status=None, stream=None):
+        """Launch the row gather behind whatever fills `result` (same stream,
+        no host sync): rows ids[0 .. n) of the batch `out`, in that order, as
+        a new compact CSR.  `ids` is a device int32 or int64 tensor (read as
+        unsigned; an id at or past the batch's rows gives an empty row and is
+        counted).  `dst` is an alloc()-style dict sized by the caller; the
+        default holds len(ids) rows and as many entries as the whole source
+        (out["counts"]), which is enough when no id repeats.  Returns (dst,
+        dst_result, status): the device result block (dmlc_amd_result layout:
+        exact counts, error) and the device status tensor (int64[4]: rows
+        written, bad ids, first bad position, GATHER_FLAG_* bits).  dst and
+        dst_result go straight into to_dense_async or another gather."""
+        torch = self.torch
+        if ids.dim() != 1 or ids.dtype not in (torch.int32, torch.int64) or not ids.is_contiguous():
+            raise ValueError("ids must be a contiguous 1-D device int32 or int64 tensor")
+        n = int(ids.numel())
+        if dst is None:
+            c = list(out["counts"]) + [0] * (8 - len(out["counts"]))
+            for slot in (ROWS, WEIGHT, QID, LABEL):
+                c[slot] = n
+            c[VALUE] = c[FIELD] = c[INDEX]  # (which per-entry arrays exist is known on the device)
+            dst = self.alloc(c)
+        if dst_result is None:
+            dst_result = torch.empty(16, dtype=torch.int64, device=ids.device)
+        if status is None:
+            status = torch.empty(4, dtype=torch.int64, device=ids.device)
+        need = lib().dmlc_amd_gather_workspace_bytes(n)
+        if self._gws is None or self._gws.numel() < need:
+            self._gws = torch.empty(need, dtype=torch.uint8, device="cuda")
+        p = GatherParams()
+        p.index_bits = self.params.index_bits
+        p.value_type = p.label_type = self._value_type()
+        p.id_bits = 64 if ids.dtype == torch.int64 else 32
+        p.flags = self.params.flags & FLAG_MAX_INDEX
+        s = stream if stream is not None else torch.cuda.current_stream()
+        rc = lib().dmlc_amd_gather_rows(ctypes.byref(out.get("_csr") or self.csr_of(out)), result.data_ptr(),
+                                        ids.data_ptr() if n else None, n, ctypes.byref(p),
+                                        ctypes.byref(dst.get("_csr") or self.csr_of(dst)), dst_result.data_ptr(),
+                                        status.data_ptr(), self._gws.data_ptr(), self._gws.numel(), s.cuda_stream)
+        if rc != 0:
+            msg = lib().dmlc_amd_error_string(rc).decode()
+            if rc == 33:
+                msg += " (%s)" % lib().dmlc_amd_last_hip_error().decode()
+            raise RuntimeError("dmlc_amd_gather_rows: %s" % msg)
+        return dst, dst_result, status
+
+    def gather_rows(self, out, ids):
+        """Rows `ids` of a batch returned by parse() (or by gather_rows): sizes
+        the new batch exactly, syncs, and returns a dict shaped like parse()'s
+        (the arrays, "counts", "result", "error", "max_index", ...) with
+        "gather_status" (uint64[4]) added; to_host, to_dense and gather_rows
+        take it."""
+        torch = self.torch
+        n = int(ids.numel())
+        # the exact entry count: the selected rows' lengths (bad ids: none)
+        rows = int(out["counts"][ROWS])
+        if n and rows:
+            r = ids.long()
+            ok = (r >= 0) & (r < rows)
+            r = torch.where(ok, r, torch.zeros_like(r))
+            off = out["offset"]
+            nnz = int(torch.where(ok, off[r + 1] - off[r], torch.zeros_like(r)).sum().item())
+        else:
+            nnz = 0
+        sc = out["counts"]
+        c = [0] * 8
+        c[ROWS], c[INDEX] = n, nnz
+        c[VALUE] = nnz if sc[VALUE] else 0
+        c[FIELD] = nnz if sc[FIELD] else 0
+        for slot in (WEIGHT, QID, LABEL):
+            c[slot] = n if sc[slot] and sc[slot] == sc[ROWS] else 0
+        dst = self.alloc(c)
+        _, res, status = self.gather_rows_async(out, out["result"], ids, dst=dst)
+        r = res.cpu().numpy().view(np.uint64)
+        dst["counts"] = [int(x) for x in r[:8]]
+        dst["result_counts"] = list(dst["counts"])
+        dst["error"], dst["path"] = int(r[8]), int(r[9])
+        dst["max_index"], dst["max_field"] = int(r[10]), int(r[11])
+        dst["result"] = res
+        dst["gather_status"] = status.cpu().numpy().view(np.uint64)
+        return dst
+
+    def shuffle(self, out, generator=None):
+        """The batch with its rows in a fresh random order (torch.randperm on
+        the device): (batch, permutation); batch row i is out's row perm[i]."""
+        torch = self.torch
+        perm = torch.randperm(int(out["counts"][ROWS]), device="cuda", generator=generator)
+        return self.gather_rows(out, perm), perm
 
 
 def build_id():

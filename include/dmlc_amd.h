@@ -188,6 +188,84 @@ int dmlc_amd_to_dense(const dmlc_amd_csr *csr, const dmlc_amd_result *d_result,
  * (either pointer may be NULL). */
 int dmlc_amd_dense_geometry(uint32_t *cells_per_tile, uint32_t *rows_per_tile);
 
+/* Row gather of a parsed CSR: rows ids[0 .. n_ids) of `src`, in that order,
+ * as a new compact CSR in `dst` (a shuffle, a subsample, a split; the device
+ * form of RowBlockContainer::Push(Row) row by row, src/data/row_block.h).  With
+ * rows = min(src_result.count[ROWS], src.cap[ROWS]):
+ *
+ *   dst.offset[0] = 0
+ *   for i in 0 .. n_ids-1:
+ *     r = ids[i]                                   (unsigned, compared as 64-bit)
+ *     if r >= rows: bad += 1; first_bad = min(first_bad, i); the row is empty,
+ *                   its label / weight / qid bits are 0
+ *     else: append index / value / field[src.offset[r] .. src.offset[r+1]) to dst,
+ *           label / weight / qid[i] = src ...[r]
+ *     dst.offset[i+1] = entries so far
+ *
+ * A per-row array (label, weight, qid) is there iff its count in
+ * *d_src_result is non-zero and equals count[ROWS]; a per-entry array (value,
+ * field) iff its count is non-zero (it then equals count[INDEX], or flag bit 1
+ * is raised).  Arrays that are not there are neither read nor written and
+ * their count in *d_dst_result is 0.  Everything moves as bit patterns; an id
+ * may repeat.  As in dmlc_amd_csr, cap[ROWS] is the capacity of label (and
+ * offset holds cap[ROWS] + 1 words); a null array pointer has capacity 0, and
+ * a source element at or past its capacity reads as 0.
+ *
+ * *d_dst_result has the layout a parse leaves: count[] = exact totals, even
+ * past a capacity; path = 0; error = 0, or (i << 16) | DMLC_AMD_ERR_CAPACITY
+ * with i the first position of ids whose row or entries did not fit -- nothing
+ * at or past a capacity is written; max_index / max_field = 0, or with
+ * DMLC_AMD_FLAG_MAX_INDEX the maxima of the dst arrays as written.  `dst` and
+ * *d_dst_result can go straight into dmlc_amd_to_dense or another gather.
+ *
+ * Source and destination arrays must not overlap (undefined; the same pointer
+ * on both sides is refused). */
+typedef struct dmlc_amd_gather_params {
+  int32_t index_bits;  /* 32 | 64 */
+  int32_t value_type;  /* DMLC_AMD_F32 | I32 | I64: width of value[] */
+  int32_t label_type;  /* width of label[]: F32 for libsvm/libfm, the DType for csv */
+  int32_t id_bits;     /* 32 | 64: element type of d_ids */
+  uint32_t flags;      /* 0 | DMLC_AMD_FLAG_MAX_INDEX */
+  uint32_t reserved[3];
+} dmlc_amd_gather_params;
+
+/* d_status: uint64_t[4] in device memory, set by the call itself */
+enum {
+  DMLC_AMD_GATHER_ROWS = 0,  /* rows written: min(n_ids, dst.cap[ROWS]) (0 with flag bits 0 / 1) */
+  DMLC_AMD_GATHER_BAD = 1,   /* ids at or past the source's rows */
+  DMLC_AMD_GATHER_FIRST = 2, /* smallest position i of such an id, ~0 if none */
+  DMLC_AMD_GATHER_FLAGS = 3  /* DMLC_AMD_GATHER_FLAG_* */
+};
+#define DMLC_AMD_GATHER_FLAG_ERROR 1u      /* src_result.error != 0: nothing is written, the dst counts are 0
+                                              and dst_result.error is the source's */
+#define DMLC_AMD_GATHER_FLAG_COUNT 2u      /* count[VALUE] or count[FIELD] is neither 0 nor count[INDEX]
+                                              (GetBlock's CHECK, row_block.h:171-189): nothing is written, the
+                                              dst counts are 0, dst_result.error is DMLC_AMD_ERR_ARG unless
+                                              bit 0 is set too */
+#define DMLC_AMD_GATHER_FLAG_OFFSET_CAP 4u /* a source offset pointed past the index (value, field) capacity:
+                                              it is clamped, no element at or past the capacity is read */
+#define DMLC_AMD_GATHER_FLAG_CAPACITY 8u   /* a dst capacity was exceeded (dst_result.error says where) */
+
+/* Bytes of device workspace a gather of n_ids rows needs. */
+size_t dmlc_amd_gather_workspace_bytes(uint64_t n_ids);
+
+/* Asynchronous on `stream`, after whatever fills *d_src_result; no host
+ * synchronisation, allocation or device-wide barrier, and no workgroup waits
+ * for another.  The capacities bound every read and write.  Returns
+ * DMLC_AMD_ERR_ARG before any HIP call for a null pointer (d_ids may be NULL
+ * when n_ids == 0), bad index_bits / value_type / label_type / id_bits, a
+ * non-zero reserved word or an unknown flag, a workspace that is too small,
+ * more tiles than one launch holds (2^31 - 1; see dmlc_amd_gather_geometry),
+ * or a dst array (or result block) that is the src's.  n_ids == 0 sets
+ * d_status, dst.offset[0] and the result block only. */
+int dmlc_amd_gather_rows(const dmlc_amd_csr *src, const dmlc_amd_result *d_src_result, const void *d_ids,
+                         uint64_t n_ids, const dmlc_amd_gather_params *prm, const dmlc_amd_csr *dst,
+                         dmlc_amd_result *d_dst_result, uint64_t *d_status, void *d_workspace,
+                         size_t workspace_bytes, void *stream);
+
+/* Ids per tile (one workgroup) this library was built with (the pointer may be NULL). */
+int dmlc_amd_gather_geometry(uint32_t *rows_per_tile);
+
 /* Batch dmlc::strtof (ParseFloat<float>, strtonum.h:95-264, :279-281): string i
  * is d_text[d_offsets[i] .. d_offsets[i+1]) read as NUL-terminated at its end.
  * Writes the value, the bytes consumed (endptr - nptr) and the "Invalid NAN
