@@ -548,6 +548,126 @@ int dmlc_amd_gather_rows(const dmlc_amd_csr *src, const dmlc_amd_result *d_src_r
   return e == hipSuccess ? DMLC_AMD_OK : DMLC_AMD_ERR_HIP;
 }
 
+int dmlc_amd_csc_geometry(uint32_t *entries_per_tile, uint32_t *radix_bits) {
+  if (entries_per_tile) *entries_per_tile = dmlc_amd::kCscTile;
+  if (radix_bits) *radix_bits = dmlc_amd::kCscRadixBits;
+  return DMLC_AMD_OK;
+}
+
+namespace {
+// the workspace of a CSC call (csc_core.h), every part in whole 256-byte lines:
+// meta, the digit totals, the tile records, the histogram, and with more than
+// one pass the two payload buffers (the second holds only columns for two passes)
+struct CscLayout {
+  uint64_t ntiles, passes;
+  uint64_t total, rec, hist, buf[2][4];  // byte offsets; buf[b] = col, row, rpos, val
+  uint64_t bytes;
+};
+bool csc_prm_ok(const dmlc_amd_csc_params *prm) {
+  if (!prm) return false;
+  if (prm->index_bits != 32 && prm->index_bits != 64) return false;
+  if (prm->value_type < DMLC_AMD_F32 || prm->value_type > DMLC_AMD_I64) return false;
+  if (prm->ncol == 0 || prm->ncol > (1ull << 32)) return false;
+  if (prm->flags || prm->reserved[0] || prm->reserved[1] || prm->reserved[2]) return false;
+  return true;
+}
+CscLayout csc_layout(uint64_t m, uint64_t ncol, int vbytes) {
+  CscLayout L;
+  std::memset(&L, 0, sizeof(L));
+  auto up = [](uint64_t b) { return (b + 255) & ~255ull; };
+  L.ntiles = m / dmlc_amd::kCscTile + (m % dmlc_amd::kCscTile != 0);
+  if (L.ntiles == 0) L.ntiles = 1;  // the first tile also stores col_offset
+  L.passes = dmlc_amd::csc_passes(ncol);
+  uint64_t at = 256;  // meta
+  L.total = at;
+  at += up(dmlc_amd::kCscDigits * 4);
+  L.rec = at;
+  at += up(L.ntiles * dmlc_amd::kCscRecWords * 8);
+  L.hist = at;
+  at += up(L.ntiles * dmlc_amd::kCscDigits * 4);
+  if (L.passes > 1)
+    for (int b = 0; b < 2; ++b) {
+      const bool full = b == 0 || L.passes > 2;
+      L.buf[b][0] = at;
+      at += up(m * 4);
+      if (!full) continue;
+      L.buf[b][1] = at;
+      at += up(m * 4);
+      L.buf[b][2] = at;
+      at += up(m * 4);
+      L.buf[b][3] = at;
+      at += up(m * (uint64_t)vbytes);
+    }
+  L.bytes = at;
+  return L;
+}
+}  // namespace
+
+size_t dmlc_amd_csc_workspace_bytes(uint64_t max_entries, uint64_t ncol, const dmlc_amd_csc_params *prm) {
+  if (!csc_prm_ok(prm) || ncol == 0 || ncol > (1ull << 32) || max_entries >= dmlc_amd::kCscMaxWindow) return 0;
+  return (size_t)csc_layout(max_entries, ncol, prm->value_type == DMLC_AMD_I64 ? 8 : 4).bytes;
+}
+
+int dmlc_amd_to_csc(const dmlc_amd_csr *csr, const dmlc_amd_result *d_result, const dmlc_amd_csc_params *prm,
+                    const dmlc_amd_csc *csc, uint64_t *d_status, void *d_workspace, size_t workspace_bytes,
+                    void *stream) {
+  if (!csr || !d_result || !prm || !csc || !d_status || !d_workspace) return DMLC_AMD_ERR_ARG;
+  if (!csc->col_offset || !csc->row) return DMLC_AMD_ERR_ARG;
+  if (!csc_prm_ok(prm)) return DMLC_AMD_ERR_ARG;
+  // the rows and entries the window can hold: the parsed counts are known on
+  // the device only, so tiles are launched for the bound and leave early past them
+  const uint64_t cap_rows = csr->offset ? csr->cap[DMLC_AMD_ROWS] : 0;
+  const uint64_t cap_index = csr->index ? csr->cap[DMLC_AMD_INDEX] : 0;
+  const uint64_t nrows = prm->row_begin < cap_rows ? dmlc_amd::mn<uint64_t>(prm->max_rows, cap_rows - prm->row_begin) : 0;
+  const uint64_t m = prm->max_entries ? dmlc_amd::mn<uint64_t>(prm->max_entries, cap_index) : cap_index;
+  if (nrows >= dmlc_amd::kCscMaxWindow || m >= dmlc_amd::kCscMaxWindow) return DMLC_AMD_ERR_ARG;
+  const int vbytes = prm->value_type == DMLC_AMD_I64 ? 8 : 4;
+  const CscLayout L = csc_layout(m, prm->ncol, vbytes);
+  if (workspace_bytes < L.bytes) return DMLC_AMD_ERR_ARG;
+  const void *srcs[] = {csr->offset, csr->label, csr->weight, csr->qid, csr->field, csr->index, csr->value, d_result};
+  const void *outs[] = {csc->col_offset, csc->row, csc->value, csc->pos, d_status, d_workspace};
+  for (const void *o : outs)
+    for (const void *s : srcs)
+      if (same_array(o, s)) return DMLC_AMD_ERR_ARG;
+  dmlc_amd::CscArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.offset = csr->offset;
+  a.index = csr->index;
+  a.value = csr->value;
+  a.res = reinterpret_cast<const uint64_t *>(d_result);
+  a.cap_rows = cap_rows;
+  a.cap_index = cap_index;
+  a.cap_value = csr->value ? csr->cap[DMLC_AMD_VALUE] : 0;
+  a.row_begin = prm->row_begin;
+  a.row_end = prm->row_begin + prm->max_rows < prm->row_begin ? ~0ull : prm->row_begin + prm->max_rows;
+  a.ncol = prm->ncol;
+  a.max_entries = m;
+  a.ntiles = L.ntiles;
+  a.passes = (uint32_t)L.passes;
+  a.col_offset = csc->col_offset;
+  a.row = csc->row;
+  a.val = csc->value;
+  a.pos = csc->pos;
+  a.cap = csc->cap;
+  a.status = d_status;
+  char *ws = static_cast<char *>(d_workspace);
+  a.meta = reinterpret_cast<uint64_t *>(ws);
+  a.total = reinterpret_cast<uint32_t *>(ws + L.total);
+  a.rec = reinterpret_cast<uint64_t *>(ws + L.rec);
+  a.hist = reinterpret_cast<uint32_t *>(ws + L.hist);
+  if (L.passes > 1)
+    for (int b = 0; b < 2; ++b) {
+      a.buf[b].col = reinterpret_cast<uint32_t *>(ws + L.buf[b][0]);
+      if (b == 1 && L.passes == 2) continue;
+      a.buf[b].row = reinterpret_cast<uint32_t *>(ws + L.buf[b][1]);
+      a.buf[b].rpos = reinterpret_cast<uint32_t *>(ws + L.buf[b][2]);
+      a.buf[b].val = ws + L.buf[b][3];
+    }
+  const hipError_t e = dmlc_amd::launch_csc(a, prm->index_bits == 64, vbytes, reinterpret_cast<hipStream_t>(stream));
+  g_last_hip = e;
+  return e == hipSuccess ? DMLC_AMD_OK : DMLC_AMD_ERR_HIP;
+}
+
 const char *dmlc_amd_last_hip_error(void) { return hipGetErrorString(g_last_hip); }
 
 }  // extern "C"

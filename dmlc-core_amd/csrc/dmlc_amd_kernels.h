@@ -7,6 +7,7 @@
 #include "args.h"
 #include "dense_core.h"
 #include "gather_core.h"
+#include "csc_core.h"
 
 namespace dmlc_amd {
 
@@ -42,5 +43,8 @@ hipError_t launch_dense(const DenseArgs &a, int wide, int value_bytes, uint32_t 
 // row gather of a CSR (gather_core.h): the tiles' lengths, their scan (d_status, the dst result
 // block), the copy; a.ntiles == 0 runs the scan alone
 hipError_t launch_gather(const GatherArgs &a, int wide, int value_bytes, hipStream_t s);
+// CSC transpose of a CSR's row window (csc_core.h): hist, scan, scatter per digit pass (a.passes,
+// a.ntiles >= 1 tiles each), then col_offset from the sorted columns when there are several passes
+hipError_t launch_csc(const CscArgs &a, int wide, int value_bytes, hipStream_t s);
 
 }  // namespace dmlc_amd

@@ -53,6 +53,23 @@ class GatherParams(ctypes.Structure):
                 ("id_bits", ctypes.c_int32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
 
 
+class CscParams(ctypes.Structure):
+    """dmlc_amd_csc_params (56 bytes)."""
+    _fields_ = [("index_bits", ctypes.c_int32), ("value_type", ctypes.c_int32),
+                ("row_begin", ctypes.c_uint64), ("max_rows", ctypes.c_uint64), ("ncol", ctypes.c_uint64),
+                ("max_entries", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
+class Csc(ctypes.Structure):
+    """dmlc_amd_csc."""
+    _fields_ = [("col_offset", ctypes.c_void_p), ("row", ctypes.c_void_p), ("value", ctypes.c_void_p),
+                ("pos", ctypes.c_void_p), ("cap", ctypes.c_uint64)]
+
+
+# d_status words of dmlc_amd_to_csc and its flag bits
+CSC_KEPT, CSC_DROPPED, CSC_FIRST, CSC_FLAGS = range(4)
+CSC_FLAG_ERROR, CSC_FLAG_VALUE_COUNT, CSC_FLAG_OFFSET_CAP, CSC_FLAG_CAPACITY, CSC_FLAG_MAX_ENTRIES = 1, 2, 4, 8, 16
+
 # d_status words of dmlc_amd_gather_rows and its flag bits
 GATHER_ROWS, GATHER_BAD, GATHER_FIRST, GATHER_FLAGS = range(4)
 GATHER_FLAG_ERROR, GATHER_FLAG_COUNT, GATHER_FLAG_OFFSET_CAP, GATHER_FLAG_CAPACITY = 1, 2, 4, 8
@@ -120,6 +137,15 @@ def lib():
                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
             L.dmlc_amd_gather_geometry.restype = ctypes.c_int
             L.dmlc_amd_gather_geometry.argtypes = [ctypes.POINTER(ctypes.c_uint32)]
+        if hasattr(L, "dmlc_amd_to_csc"):  # (A/B builds of older sources lack it)
+            L.dmlc_amd_csc_workspace_bytes.restype = ctypes.c_size_t
+            L.dmlc_amd_csc_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(CscParams)]
+            L.dmlc_amd_to_csc.restype = ctypes.c_int
+            L.dmlc_amd_to_csc.argtypes = [ctypes.POINTER(Csr), ctypes.c_void_p, ctypes.POINTER(CscParams),
+                                          ctypes.POINTER(Csc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                          ctypes.c_void_p]
+            L.dmlc_amd_csc_geometry.restype = ctypes.c_int
+            L.dmlc_amd_csc_geometry.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
         L.dmlc_amd_profile_begin.restype = ctypes.c_int
         L.dmlc_amd_profile_end.restype = ctypes.c_int
         L.dmlc_amd_profile_end.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int),
@@ -145,7 +171,16 @@ EXPORTED_SYMBOLS = ("dmlc_amd_parse", "dmlc_amd_workspace_bytes", "dmlc_amd_erro
                     "dmlc_amd_profile_begin", "dmlc_amd_profile_end", "dmlc_amd_last_hip_error",
                     "dmlc_amd_copy", "dmlc_amd_copy_n", "dmlc_amd_copy_n_dev", "dmlc_amd_fast_geometry",
                     "dmlc_amd_build_id", "dmlc_amd_to_dense", "dmlc_amd_dense_geometry", "dmlc_amd_gather_rows",
-                    "dmlc_amd_gather_workspace_bytes", "dmlc_amd_gather_geometry")
+                    "dmlc_amd_gather_workspace_bytes", "dmlc_amd_gather_geometry", "dmlc_amd_to_csc",
+                    "dmlc_amd_csc_workspace_bytes", "dmlc_amd_csc_geometry")
+
+
+def csc_geometry():
+    """(entries per tile, bits per digit pass) of dmlc_amd_to_csc in the loaded
+    library (dmlc_amd_csc_geometry)."""
+    t, b = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    lib().dmlc_amd_csc_geometry(ctypes.byref(t), ctypes.byref(b))
+    return int(t.value), int(b.value)
 
 
 def dense_geometry():
@@ -227,6 +262,7 @@ class DeviceParser:
         self.torch = _torch()
         self._ws = None
         self._gws = None  # gather_rows_async's workspace
+        self._cws = None  # to_csc_async's
 
     def _workspace(self, nbytes, nchunks):
         need = lib().dmlc_amd_workspace_bytes(nbytes, nchunks, ctypes.byref(self.params))
@@ -501,6 +537,90 @@ class DeviceParser:
         dst["result"] = res
         dst["gather_status"] = status.cpu().numpy().view(np.uint64)
         return dst
+
+    # ---- the column view: CSC transpose of a parsed batch (dmlc_amd_to_csc)
+    def to_csc_async(self, out, result, csc, status=None, *, ncol, row_begin=0, max_rows=None, stream=None):
+        """Launch the CSC transpose behind whatever fills `result` (same
+        stream, no host sync): the entries of rows [row_begin, row_begin +
+        max_rows) of the batch `out` by column, each column in ascending
+        source position.  `csc` is a dict of device tensors: "col_offset"
+        (int64[ncol + 1]), "row" (int32[cap]), and optionally "value" (the
+        value dtype, [cap]) and "pos" (int64[cap], each entry's source
+        position); cap is the length of "row".  max_rows defaults to every row
+        from row_begin on.  Returns the device status tensor (int64[4]:
+        entries kept, entries dropped, first dropped position, CSC_FLAG_*
+        bits)."""
+        torch = self.torch
+        vt = self._value_type()
+        co, row, val, pos = csc["col_offset"], csc["row"], csc.get("value"), csc.get("pos")
+        if co.dtype != torch.int64 or int(co.numel()) < int(ncol) + 1 or not co.is_contiguous():
+            raise ValueError("col_offset must be a contiguous int64 tensor of ncol + 1 = %d words" % (int(ncol) + 1))
+        if row.dtype != torch.int32 or not row.is_contiguous():
+            raise ValueError("row must be a contiguous int32 tensor")
+        cap = int(row.numel())
+        if val is not None and (val.dtype != _vdt(torch, vt) or int(val.numel()) < cap or not val.is_contiguous()):
+            raise ValueError("value must be a contiguous %s tensor of at least len(row) elements" % _vdt(torch, vt))
+        if pos is not None and (pos.dtype != torch.int64 or int(pos.numel()) < cap or not pos.is_contiguous()):
+            raise ValueError("pos must be a contiguous int64 tensor of at least len(row) elements")
+        if status is None:
+            status = torch.empty(4, dtype=torch.int64, device=co.device)
+        p = CscParams()
+        p.index_bits = self.params.index_bits
+        p.value_type = vt
+        p.row_begin = int(row_begin)
+        p.max_rows = (1 << 64) - 1 if max_rows is None else int(max_rows)
+        p.ncol = int(ncol)
+        src = out.get("_csr") or self.csr_of(out)
+        m = int(src.cap[INDEX])
+        p.max_entries = m
+        need = lib().dmlc_amd_csc_workspace_bytes(m, int(ncol), ctypes.byref(p))
+        if need == 0:
+            raise ValueError("dmlc_amd_to_csc: bad ncol = %d or a batch of 2^32 - 1 or more entries" % int(ncol))
+        if self._cws is None or self._cws.numel() < need:
+            self._cws = torch.empty(need, dtype=torch.uint8, device="cuda")
+        c = Csc()
+        c.col_offset, c.row = co.data_ptr(), row.data_ptr() if cap else status.data_ptr()
+        c.value = val.data_ptr() if val is not None and cap else None
+        c.pos = pos.data_ptr() if pos is not None and cap else None
+        c.cap = cap
+        s = stream if stream is not None else torch.cuda.current_stream()
+        rc = lib().dmlc_amd_to_csc(ctypes.byref(src), result.data_ptr(), ctypes.byref(p), ctypes.byref(c),
+                                   status.data_ptr(), self._cws.data_ptr(), self._cws.numel(), s.cuda_stream)
+        if rc != 0:
+            msg = lib().dmlc_amd_error_string(rc).decode()
+            if rc == 33:
+                msg += " (%s)" % lib().dmlc_amd_last_hip_error().decode()
+            raise RuntimeError("dmlc_amd_to_csc: %s" % msg)
+        return status
+
+    def to_csc(self, out, ncol=None, want_pos=False):
+        """The column view of a batch returned by parse() or gather_rows():
+        a dict with "col_offset" (int64[ncol + 1]), "row" (int32), "value"
+        (None for a batch without values) and, with want_pos, "pos" (int64:
+        each entry's position in the batch's arrays, e.g. out["field"][pos]),
+        trimmed to the kept entries after a sync; "status" is uint64[4].
+        ncol=None means max_index + 1, which needs a parser made with
+        flags=FLAG_MAX_INDEX."""
+        torch = self.torch
+        if ncol is None:
+            if not self.params.flags & FLAG_MAX_INDEX:
+                raise ValueError("ncol=None needs a parse made with FLAG_MAX_INDEX (result.max_index)")
+            ncol = int(out["max_index"]) + 1
+        c = out["counts"]
+        cap = int(c[INDEX])
+        csc = {"col_offset": torch.empty(int(ncol) + 1, dtype=torch.int64, device="cuda"),
+               "row": torch.empty(cap, dtype=torch.int32, device="cuda")}
+        if c[VALUE]:
+            csc["value"] = torch.empty(cap, dtype=_vdt(torch, self._value_type()), device="cuda")
+        if want_pos:
+            csc["pos"] = torch.empty(cap, dtype=torch.int64, device="cuda")
+        status = self.to_csc_async(out, out["result"], csc, ncol=ncol).cpu().numpy().view(np.uint64)
+        kept = min(int(status[CSC_KEPT]), cap)
+        res = {"col_offset": csc["col_offset"], "row": csc["row"][:kept],
+               "value": csc["value"][:kept] if "value" in csc else None, "status": status, "ncol": int(ncol)}
+        if want_pos:
+            res["pos"] = csc["pos"][:kept]
+        return res
 
     def shuffle(self, out, generator=None):
         """The batch with its rows in a fresh random order (torch.randperm on

@@ -266,6 +266,92 @@ int dmlc_amd_gather_rows(const dmlc_amd_csr *src, const dmlc_amd_result *d_src_r
 /* Ids per tile (one workgroup) this library was built with (the pointer may be NULL). */
 int dmlc_amd_gather_geometry(uint32_t *rows_per_tile);
 
+/* CSC transpose of a parsed CSR: the entries of rows [row_begin, row_begin +
+ * max_rows) by column, a stable counting sort (what SparsePage::GetTranspose
+ * does on the host; the column view a tree or coordinate-descent learner
+ * reads).  `csr` and *d_result are a parse's or a gather's, unchanged.  With
+ * rows = min(result.count[ROWS], csr.cap[ROWS]) and r1 = min(rows, row_begin +
+ * max_rows):
+ *
+ *   kept = dropped = 0; first = ~0
+ *   for r in row_begin .. r1-1:
+ *     for k in offset[r] .. offset[r+1]-1, ascending:   (offsets clamped to the index / value
+ *       c = index[k]            (compared as 64-bit)     capacity: flag bit 2, as in to_dense)
+ *       if c >= ncol: dropped += 1; first = min(first, k)
+ *       else: append (row = r - row_begin, value[k], pos = k) to column c
+ *   col_offset[c] = entries of columns < c, for c in 0 .. ncol      (col_offset[ncol] = kept)
+ *
+ * The entries of a column stand in ascending source position k: ascending
+ * row, duplicates of one cell in file order.  This is the only order the call
+ * produces; two runs give the same bytes.  `value` (elements of the value type,
+ * moved as bit patterns) is neither read nor written when count[VALUE] == 0 or
+ * csc.value is NULL.  `pos`, when not NULL, receives each output entry's
+ * absolute source position k, so anything else that is per entry (libfm's
+ * field) follows by one index_select; the field array itself is ignored.  `cap`
+ * bounds row, value and pos in entries: with kept > cap nothing at or past cap
+ * is written, col_offset and the status stay exact and flag bit 3 is set.  All
+ * ncol + 1 words of col_offset are written whatever the input.  max_rows == 0
+ * or row_begin >= rows gives an empty CSC (col_offset all 0, kept = 0).  The
+ * offsets of a parse or a gather never descend; for other offsets no access
+ * leaves the capacities and the content is unspecified. */
+typedef struct dmlc_amd_csc {
+  uint64_t *col_offset; /* ncol + 1 words */
+  uint32_t *row;        /* cap */
+  void *value;          /* cap elements of the value type, or NULL */
+  uint64_t *pos;        /* cap, or NULL */
+  uint64_t cap;
+} dmlc_amd_csc;
+
+typedef struct dmlc_amd_csc_params {
+  int32_t index_bits; /* 32 | 64 */
+  int32_t value_type; /* DMLC_AMD_F32 | I32 | I64: width of value[] */
+  uint64_t row_begin, max_rows;
+  uint64_t ncol;        /* 1 .. 2^32 */
+  uint64_t max_entries; /* the caller's bound on the window's entries: the launches and the workspace are
+                           sized by it; 0 = csr.cap[INDEX] */
+  uint32_t flags, reserved[3]; /* 0 */
+} dmlc_amd_csc_params;
+
+/* d_status: uint64_t[4] in device memory, set by the call itself */
+enum {
+  DMLC_AMD_CSC_KEPT = 0,    /* entries with index < ncol (exact, also past cap; 0 with flag bits 0 / 1) */
+  DMLC_AMD_CSC_DROPPED = 1, /* entries dropped because index >= ncol */
+  DMLC_AMD_CSC_FIRST = 2,   /* smallest position k of a dropped entry, ~0 if none */
+  DMLC_AMD_CSC_FLAGS = 3    /* DMLC_AMD_CSC_FLAG_* (bits 0 - 2 as the dense and gather flags) */
+};
+#define DMLC_AMD_CSC_FLAG_ERROR 1u       /* result.error != 0: nothing is written but col_offset, all 0 */
+#define DMLC_AMD_CSC_FLAG_VALUE_COUNT 2u /* count[VALUE] is neither 0 nor count[INDEX]: likewise */
+#define DMLC_AMD_CSC_FLAG_OFFSET_CAP 4u  /* an offset pointed past the index (or value) capacity: it is
+                                            clamped, no element at or past the capacity is read */
+#define DMLC_AMD_CSC_FLAG_CAPACITY 8u    /* kept > csc.cap */
+#define DMLC_AMD_CSC_FLAG_MAX_ENTRIES 16u /* the window holds more than max_entries entries: only its first
+                                             max_entries were transposed (a caller's error) */
+
+/* Bytes of device workspace a call with this bound on the window's entries
+ * (not 0 here: pass csr.cap[INDEX] for the default) and these parameters
+ * needs; 0 for parameters the call would refuse. */
+size_t dmlc_amd_csc_workspace_bytes(uint64_t max_entries, uint64_t ncol, const dmlc_amd_csc_params *prm);
+
+/* Asynchronous on `stream`, after whatever fills *d_result: a fixed sequence of
+ * plain launches (three per 8-bit digit of ncol - 1, see dmlc_amd_csc_geometry),
+ * no host synchronisation, allocation or device-wide barrier, and no workgroup
+ * waits for another.  The capacities bound every read and write.  Returns
+ * DMLC_AMD_ERR_ARG before any HIP call for a null pointer (csc.pos, and
+ * csc.value when the caller has none, may be NULL), ncol == 0 or ncol > 2^32,
+ * bad index_bits / value_type, a non-zero reserved word or an unknown flag, a
+ * workspace that is too small, an output (or the workspace) that is one of the
+ * source's arrays or its result block, or a window that can hold 2^32 - 1 or
+ * more rows or entries (min(max_rows, cap[ROWS] - row_begin) rows, max_entries
+ * entries: split the rows over several calls) -- which keeps `row` and the
+ * internal positions at 32 bits. */
+int dmlc_amd_to_csc(const dmlc_amd_csr *csr, const dmlc_amd_result *d_result, const dmlc_amd_csc_params *prm,
+                    const dmlc_amd_csc *csc, uint64_t *d_status, void *d_workspace, size_t workspace_bytes,
+                    void *stream);
+
+/* Entries per tile (one workgroup) and bits per digit pass this library was
+ * built with (either pointer may be NULL). */
+int dmlc_amd_csc_geometry(uint32_t *entries_per_tile, uint32_t *radix_bits);
+
 /* Batch dmlc::strtof (ParseFloat<float>, strtonum.h:95-264, :279-281): string i
  * is d_text[d_offsets[i] .. d_offsets[i+1]) read as NUL-terminated at its end.
  * Writes the value, the bytes consumed (endptr - nptr) and the "Invalid NAN
