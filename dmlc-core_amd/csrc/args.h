@@ -101,7 +101,7 @@ struct FastSvmArgs {
   uint32_t *gate;       // != 0: input left the grammar -> exact path
   unsigned long long *err;  // first error of this path
   uint64_t *res;        // dmlc_amd_result counts (written by the last tile)
-  uint32_t *ticket;     // persistent launch: tiles handed out past the first gridDim.x (zeroed per launch)
+  uint32_t *reserved;   // unused, null (without it the kernels' argument loads move, and their schedule with them)
   // the lean kernel (svm_lean.h) ahead of this one: its look-back words [5 ntiles]
   // and ~(its first poisoned tile) (0: none), zeroed per launch.  The full
   // kernel resumes at that tile, its look-back seeded by the lean inclusive
@@ -111,7 +111,7 @@ struct FastSvmArgs {
 };
 
 // look-back words per single-pass tile (fast_common.h: status + 4 prefix words);
-// the persistent launch's ticket word follows them
+// one reserved word follows them, zeroed with them (lean_lb keeps its address)
 constexpr uint64_t kFastLbWords = 5;
 // the CSV single pass (csv_fast.h csv_look_back): status + 3 prefix words in
 // one 64-byte record per tile

@@ -102,32 +102,6 @@ struct DevBlockT {
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);  // row_bcast:31
     return x;
   }
-  // Exclusive prefix sum and block total of packed counters whose fields
-  // never carry across bit 31 (the tiles' 16-bit role counts): two 32-bit
-  // DPP wave scans, one LDS round for the wave totals.
-  __device__ __forceinline__ uint64_t exclusive_add(uint64_t v, uint64_t *total) const {
-    const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-    const uint64_t inc = wave_incl_add((uint32_t)v) | ((uint64_t)wave_incl_add((uint32_t)(v >> 32)) << 32);
-    if constexpr (NW == 1) {
-      *total = shfl(inc, kWave - 1);
-      (void)lane;
-      (void)wid;
-      return inc - v;
-    }
-    if (lane == kWave - 1) scratch[wid] = inc;
-    __syncthreads();
-    uint64_t pre = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      const uint64_t t = scratch[w];
-      pre += w < wid ? t : 0;
-      tot += t;
-    }
-    *total = tot;
-    __syncthreads();
-    return pre + inc - v;
-  }
-
   // Exclusive prefix sum of packed counters (fields never carry across bit
   // 31) with one barrier, and the OR of a flag over the block: each wave's
   // total and flag go to wtot / wbad (caller's LDS, never rewritten before
@@ -153,38 +127,6 @@ struct DevBlockT {
     *total = tot;
     *wpre = pre;
     return pre + inc - v;
-  }
-
-  // The same with one barrier: every wave reads all wave totals itself.  The
-  // scratch slots stay read until the caller's next barrier, so a second
-  // scan must not follow before one.
-  template <typename T, typename Op>
-  __device__ __forceinline__ T exclusive1(T v, T identity, Op op, T *total) const {
-    static_assert(sizeof(T) <= kSlot, "scan element larger than the scratch slot");
-    const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-    T inc = v;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      T o = shfl_up(inc, d);
-      if (lane >= d) inc = op(o, inc);
-    }
-    const T up = shfl_up(inc, 1);
-    if constexpr (NW == 1) {
-      *total = shfl(inc, kWave - 1);
-      return lane == 0 ? identity : up;
-    }
-    T *sc = reinterpret_cast<T *>(scratch);
-    if (lane == kWave - 1) *reinterpret_cast<T *>(reinterpret_cast<char *>(sc) + kSlot * wid) = inc;
-    __syncthreads();
-    T pre = identity, tot = identity;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      const T t = *reinterpret_cast<T *>(reinterpret_cast<char *>(sc) + kSlot * w);
-      if (w < wid) pre = op(pre, t);
-      tot = op(tot, t);
-    }
-    *total = tot;
-    return lane == 0 ? pre : op(pre, up);
   }
 
   // Exclusive prefix (identity for thread 0) and the block total.

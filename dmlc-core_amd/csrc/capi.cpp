@@ -35,9 +35,63 @@ struct Carve {
 // Delimiters that ParseFloat / strtoll can consume, which would make the field
 // structure depend on decoding (csv_parser.h:99-127): handled by the exact
 // per-line path instead of the field-parallel one.
-bool csv_delim_fast(int d, int vtype) {
-  (void)vtype;
+bool csv_delim_fast(int d) {
   return dmlc_amd::csv_delim_plain((unsigned)d & 0xFFu);  // args.h
+}
+
+// What dmlc_amd_parse sets alike in the three exact argument blocks
+// (LibsvmArgs, CsvArgs, LibfmArgs) ...
+template <class A>
+void fill_exact_common(A &a, const void *d_text, uint64_t nbytes, const uint64_t *ucs, uint64_t nunits,
+                       const dmlc_amd::UnitLim &ul, uint64_t T, uint64_t ntiles, const dmlc_amd_params *prm,
+                       const dmlc_amd_csr *out, uint64_t *tile_cnt, uint64_t *tile_base, uint64_t *chunk_tab,
+                       uint64_t *res, uint32_t *gate, uint32_t *rec, uint32_t rec_win) {
+  std::memset(&a, 0, sizeof(a));
+  a.text = reinterpret_cast<const uint8_t *>(d_text);
+  a.n = nbytes;
+  a.cs = ucs;
+  a.nchunk = (int)nunits;
+  a.ul = ul;
+  a.tile_bytes = T;
+  a.ntiles = (uint32_t)ntiles;
+  a.wide = prm->index_bits == 64;
+  a.tile_cnt = tile_cnt;
+  a.tile_base = tile_base;
+  a.offset = out->offset;
+  a.label = static_cast<decltype(a.label)>(out->label);  // DType: float but for CSV
+  a.weight = out->weight;
+  a.index = out->index;
+  a.value = static_cast<decltype(a.value)>(out->value);
+  for (int i = 0; i < 8; ++i) a.cap[i] = out->cap[i];
+  a.chunk_tab = chunk_tab;
+  a.err = reinterpret_cast<unsigned long long *>(res + 8);
+  a.gate = gate;
+  a.rec = rec;
+  a.rec_win = rec ? rec_win : 0;
+}
+// ... and in the two single-pass ones (FastSvmArgs, FastCsvArgs)
+template <class F>
+void fill_fast_common(F &f, const void *d_text, uint64_t nbytes, const uint64_t *ucs, uint64_t nunits, uint64_t nft,
+                      const dmlc_amd_params *prm, const dmlc_amd_csr *out, int phase, uint64_t *lb, uint32_t *gate,
+                      unsigned long long *ferr, uint64_t *res) {
+  std::memset(&f, 0, sizeof(f));
+  f.text = reinterpret_cast<const uint8_t *>(d_text);
+  f.n = nbytes;
+  f.cs = ucs;
+  f.nchunk = (int)nunits;
+  f.ntiles = (uint32_t)nft;
+  f.wide = prm->index_bits == 64;
+  f.skip_if_gated = phase == dmlc_amd::kPhaseFill;
+  f.offset = out->offset;
+  f.label = reinterpret_cast<float *>(out->label);
+  f.weight = out->weight;
+  f.index = out->index;
+  f.value = static_cast<decltype(f.value)>(out->value);
+  for (int i = 0; i < 8; ++i) f.cap[i] = out->cap[i];
+  f.lb = lb;
+  f.gate = gate;
+  f.err = ferr;
+  f.res = res;
 }
 
 // ---- kernel timing (dmlc_amd_profile_begin / _end)
@@ -146,7 +200,7 @@ uint64_t rec_bytes_of(uint64_t nbytes, uint64_t T, uint64_t ntiles, const dmlc_a
   return dmlc_amd::exact_rec_on(nbytes, b) ? b : 0;
 }
 
-// single-pass look-back words: the full kernel's [5 nft] + its ticket; libsvm
+// single-pass look-back words: the full kernel's [5 nft] + a reserved word; libsvm
 // adds the lean kernel's [5 nft] + its poison word (libsvm.hip); CSV keeps
 // one 8-word record per tile (csv_fast.h csv_look_back)
 uint64_t lb_words_of(uint64_t nft, const dmlc_amd_params *prm) {
@@ -226,120 +280,46 @@ int dmlc_amd_parse(const void *d_text, uint64_t nbytes, const uint64_t *d_chunk_
   const int phase = count_only ? dmlc_amd::kPhaseCount
                                : (fill_only ? dmlc_amd::kPhaseFill : dmlc_amd::kPhaseFull);
   hipError_t e = hipSuccess;
+  uint64_t *tab = d_chunk_table ? d_chunk_table : chunk_sink;  // the exact kernels always write one
+  const bool exact_flag = (prm->flags & DMLC_AMD_FLAG_EXACT) != 0;
   if (prm->format == DMLC_AMD_LIBSVM) {
     dmlc_amd::LibsvmArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.text = reinterpret_cast<const uint8_t *>(d_text);
-    a.n = nbytes;
-    a.cs = ucs;
-    a.nchunk = (int)nunits;
-    a.ul = ul;
-    a.tile_bytes = T;
-    a.ntiles = (uint32_t)ntiles;
-    a.wide = prm->index_bits == 64;
+    fill_exact_common(a, d_text, nbytes, ucs, nunits, ul, T, ntiles, prm, out, tile_cnt, tile_base, tab, res, ctl, rec,
+                      rec_win);
     a.indexing_mode = prm->indexing_mode;
-    a.tile_cnt = tile_cnt;
-    a.tile_base = tile_base;
-    a.offset = out->offset;
-    a.label = reinterpret_cast<float *>(out->label);
-    a.weight = out->weight;
     a.qid = out->qid;
-    a.index = out->index;
-    a.value = reinterpret_cast<float *>(out->value);
-    for (int i = 0; i < 8; ++i) a.cap[i] = out->cap[i];
-    a.chunk_tab = d_chunk_table ? d_chunk_table : chunk_sink;
     a.chunk_min = chunk_min;
-    a.err = reinterpret_cast<unsigned long long *>(res + 8);
-    a.gate = ctl;
-    a.rec = rec;
     a.rec_meta = rec_meta;
-    a.rec_win = rec ? rec_win : 0;
     dmlc_amd::FastSvmArgs f;
-    std::memset(&f, 0, sizeof(f));
-    f.text = a.text;
-    f.n = nbytes;
-    f.cs = ucs;
-    f.nchunk = (int)nunits;
-    f.ntiles = (uint32_t)nft;
-    f.wide = a.wide;
+    fill_fast_common(f, d_text, nbytes, ucs, nunits, nft, prm, out, phase, lb, ctl, ferr, res);
     f.indexing_mode = prm->indexing_mode;
-    f.skip_if_gated = phase == dmlc_amd::kPhaseFill;
-    f.offset = a.offset;
-    f.label = a.label;
-    f.weight = a.weight;
-    f.qid = a.qid;
-    f.index = a.index;
-    f.value = a.value;
-    for (int i = 0; i < 8; ++i) f.cap[i] = out->cap[i];
+    f.qid = out->qid;
     // indexing_mode < 0 needs the units' index ranges after the write pass:
     // the chunk table, or the workspace's when the caller passes none
     f.chunk_tab = d_chunk_table ? d_chunk_table : (prm->indexing_mode < 0 ? chunk_sink : nullptr);
-    f.lb = lb;
-    f.ticket = reinterpret_cast<uint32_t *>(lb + nft * dmlc_amd::kFastLbWords);  // zeroed with lb
-    f.lean_lb = lb + nft * dmlc_amd::kFastLbWords + 1;
+    f.lean_lb = lb + nft * dmlc_amd::kFastLbWords + 1;  // past the reserved word after lb's records (zeroed with lb)
     f.lean_poison = f.lean_lb + nft * dmlc_amd::kFastLbWords;
     f.qsum = labsum;
     f.umin = fast_min;
-    f.gate = ctl;
-    f.err = ferr;
-    f.res = res;
-    const bool use_fast = nbytes > 0 && !(prm->flags & DMLC_AMD_FLAG_EXACT);
-    e = dmlc_amd::launch_libsvm(a, f, use_fast, res, phase, s);
+    e = dmlc_amd::launch_libsvm(a, f, nbytes > 0 && !exact_flag, res, phase, s);
   } else if (prm->format == DMLC_AMD_CSV) {
     dmlc_amd::CsvArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.text = reinterpret_cast<const uint8_t *>(d_text);
-    a.n = nbytes;
-    a.cs = ucs;
-    a.nchunk = (int)nunits;
-    a.ul = ul;
-    a.tile_bytes = T;
-    a.ntiles = (uint32_t)ntiles;
-    a.wide = prm->index_bits == 64;
+    fill_exact_common(a, d_text, nbytes, ucs, nunits, ul, T, ntiles, prm, out, tile_cnt, tile_base, tab, res, ctl, rec,
+                      rec_win);
     a.vtype = prm->value_type;
     a.label_column = prm->label_column;
     a.weight_column = prm->weight_column;
     a.delim = (uint32_t)prm->delimiter & 0xFFu;
-    a.fast_delim = csv_delim_fast(prm->delimiter, prm->value_type);
-    a.tile_cnt = tile_cnt;
-    a.tile_base = tile_base;
-    a.offset = out->offset;
-    a.label = out->label;
-    a.weight = out->weight;
-    a.index = out->index;
-    a.value = out->value;
-    for (int i = 0; i < 8; ++i) a.cap[i] = out->cap[i];
-    a.chunk_tab = d_chunk_table ? d_chunk_table : chunk_sink;
-    a.err = reinterpret_cast<unsigned long long *>(res + 8);
-    a.gate = ctl;
-    a.rec = rec;
-    a.rec_win = rec ? rec_win : 0;
+    a.fast_delim = csv_delim_fast(prm->delimiter);
     dmlc_amd::FastCsvArgs f;
-    std::memset(&f, 0, sizeof(f));
-    f.text = a.text;
-    f.n = nbytes;
-    f.cs = ucs;
-    f.nchunk = (int)nunits;
-    f.ntiles = (uint32_t)nft;
-    f.wide = a.wide;
+    fill_fast_common(f, d_text, nbytes, ucs, nunits, nft, prm, out, phase, lb, ctl, ferr, res);
     f.delim = a.delim;
-    f.skip_if_gated = phase == dmlc_amd::kPhaseFill;
     f.label_col = prm->label_column;
     // the weight column is ordinary for integer DTypes (csv_parser.h:113-114)
     f.weight_col = prm->value_type == DMLC_AMD_F32 ? prm->weight_column : -1;
     f.vtype = prm->value_type;
-    f.label = reinterpret_cast<float *>(out->label);
-    f.weight = out->weight;
     f.labsum = labsum;
-    f.offset = a.offset;
-    f.index = a.index;
-    f.value = a.value;
-    for (int i = 0; i < 8; ++i) f.cap[i] = out->cap[i];
     f.chunk_tab = d_chunk_table;
-    f.lb = lb;
-    f.gate = ctl;
-    f.err = ferr;
-    f.res = res;
     // the uniform-grammar CSV kernels: the label / weight columns they take
     // by DType, and a delimiter the number decoders cannot consume or ' ' /
     // '\t' (the whitespace mode); a.fast_delim stays the exact kernels' own
@@ -347,61 +327,22 @@ int dmlc_amd_parse(const void *d_text, uint64_t nbytes, const uint64_t *d_chunk_
     const int sp_delim = dmlc_amd::csv_single_pass_delim(a.delim);
     f.ws = sp_delim == 2;
     const bool cols_ok = dmlc_amd::csv_single_pass_columns(prm->value_type, prm->label_column, prm->weight_column);
-    const bool use_fast = nbytes > 0 && cols_ok && sp_delim != 0 && !(prm->flags & DMLC_AMD_FLAG_EXACT);
-    e = dmlc_amd::launch_csv(a, f, use_fast, res, phase, s);
+    e = dmlc_amd::launch_csv(a, f, nbytes > 0 && cols_ok && sp_delim != 0 && !exact_flag, res, phase, s);
   } else {  // DMLC_AMD_LIBFM
     dmlc_amd::LibfmArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.text = reinterpret_cast<const uint8_t *>(d_text);
-    a.n = nbytes;
-    a.cs = ucs;
-    a.nchunk = (int)nunits;
-    a.ul = ul;
-    a.tile_bytes = T;
-    a.ntiles = (uint32_t)ntiles;
-    a.wide = prm->index_bits == 64;
+    fill_exact_common(a, d_text, nbytes, ucs, nunits, ul, T, ntiles, prm, out, tile_cnt, tile_base, tab, res, ctl, rec,
+                      rec_win);
     a.indexing_mode = prm->indexing_mode;
-    a.tile_cnt = tile_cnt;
-    a.tile_base = tile_base;
-    a.offset = out->offset;
-    a.label = reinterpret_cast<float *>(out->label);
-    a.weight = out->weight;
-    a.index = out->index;
     a.field = out->field;
-    a.value = reinterpret_cast<float *>(out->value);
-    for (int i = 0; i < 8; ++i) a.cap[i] = out->cap[i];
-    a.chunk_tab = d_chunk_table ? d_chunk_table : chunk_sink;
     a.chunk_min = chunk_min;
-    a.err = reinterpret_cast<unsigned long long *>(res + 8);
-    a.gate = ctl;
-    a.rec = rec;
     a.rec_meta = rec_meta;
-    a.rec_win = rec ? rec_win : 0;
     dmlc_amd::FastSvmArgs f;  // the single-pass kernel with the libfm roles (svm_fast.h)
-    std::memset(&f, 0, sizeof(f));
-    f.text = a.text;
-    f.n = nbytes;
-    f.cs = ucs;
-    f.nchunk = (int)nunits;
-    f.ntiles = (uint32_t)nft;
-    f.wide = a.wide;
+    fill_fast_common(f, d_text, nbytes, ucs, nunits, nft, prm, out, phase, lb, ctl, ferr, res);
     f.indexing_mode = prm->indexing_mode;
-    f.skip_if_gated = phase == dmlc_amd::kPhaseFill;
-    f.offset = a.offset;
-    f.label = a.label;
-    f.weight = a.weight;
-    f.index = a.index;
-    f.field = a.field;
-    f.value = a.value;
-    for (int i = 0; i < 8; ++i) f.cap[i] = out->cap[i];
-    f.chunk_tab = prm->indexing_mode < 0 ? a.chunk_tab : d_chunk_table;  // as libsvm's
-    f.lb = lb;
+    f.field = out->field;
+    f.chunk_tab = prm->indexing_mode < 0 ? tab : d_chunk_table;  // as libsvm's
     f.umin = fast_min;
-    f.gate = ctl;
-    f.err = ferr;
-    f.res = res;
-    const bool use_fast = nbytes > 0 && !(prm->flags & DMLC_AMD_FLAG_EXACT);
-    e = dmlc_amd::launch_libfm(a, f, use_fast, res, phase, s);
+    e = dmlc_amd::launch_libfm(a, f, nbytes > 0 && !exact_flag, res, phase, s);
   }
   if (e == hipSuccess && (prm->flags & DMLC_AMD_FLAG_MAX_INDEX) && phase != dmlc_amd::kPhaseCount) {
     // NumCol of the reference's BasicRowIter: maxima of what was written

@@ -26,33 +26,10 @@ static_assert(sizeof(fcsv::Shared) + kSmallScratchU64 * 8 <= fast::kLdsBudget,
 #ifndef FCSV_MINW
 #define FCSV_MINW 6
 #endif
-template <int MODE>
-__global__ void __launch_bounds__(fast::kFThreads, FCSV_MINW) csv_fast_tile(FastCsvArgs a) {
-  __shared__ __attribute__((aligned(16))) fcsv::Shared sh;
-  __shared__ uint64_t scratch[kSmallScratchU64];
-  DevBlockS bk{scratch};
-  fcsv::tile<MODE, false, 0>(a, sh, bk, blockIdx.x);
-}
-// integer DTypes (strtoll)
-template <int MODE>
-__global__ void __launch_bounds__(fast::kFThreads, FCSV_MINW) csv_fast_tile_int(FastCsvArgs a) {
-  __shared__ __attribute__((aligned(16))) fcsv::Shared sh;
-  __shared__ uint64_t scratch[kSmallScratchU64];
-  DevBlockS bk{scratch};
-  fcsv::tile<MODE, false, 1>(a, sh, bk, blockIdx.x);
-}
-// with a label and / or weight column
-template <int MODE>
-__global__ void __launch_bounds__(fast::kFThreads, FCSV_MINW) csv_fast_tile_sp(FastCsvArgs a) {
-  __shared__ __attribute__((aligned(16))) fcsv::Shared sh;
-  __shared__ uint64_t scratch[kSmallScratchU64];
-  DevBlockS bk{scratch};
-  fcsv::tile<MODE, true, 0>(a, sh, bk, blockIdx.x);
-}
-
-// the whitespace-mode forms (delimiter ' ' or '\t', FastCsvArgs::ws) and the
-// integer label form (csv_fast.h tile<MODE, SP, VT, WS>): same launch bounds
-// and LDS as the three above
+// the single-pass kernels (csv_fast.h tile<MODE, SP, VT, WS>), one launch
+// bound and LDS for all: SP with a label and / or weight column, VT 1 the
+// integer DTypes (strtoll), WS the whitespace mode (delimiter ' ' or '\t',
+// FastCsvArgs::ws)
 #define FCSV_KERNEL(NAME, SP, VT, WS)                                                       \
   template <int MODE>                                                                       \
   __global__ void __launch_bounds__(fast::kFThreads, FCSV_MINW) NAME(FastCsvArgs a) {       \
@@ -61,6 +38,9 @@ __global__ void __launch_bounds__(fast::kFThreads, FCSV_MINW) csv_fast_tile_sp(F
     DevBlockS bk{scratch};                                                                  \
     fcsv::tile<MODE, SP, VT, WS>(a, sh, bk, blockIdx.x);                                    \
   }
+FCSV_KERNEL(csv_fast_tile, false, 0, false)
+FCSV_KERNEL(csv_fast_tile_int, false, 1, false)
+FCSV_KERNEL(csv_fast_tile_sp, true, 0, false)
 FCSV_KERNEL(csv_fast_tile_ws, false, 0, true)
 FCSV_KERNEL(csv_fast_tile_int_ws, false, 1, true)
 FCSV_KERNEL(csv_fast_tile_sp_ws, true, 0, true)
@@ -95,15 +75,6 @@ void launch_fast_tile(const FastCsvArgs &f, bool sp, hipStream_t s) {
 #undef FCSV_GO
 }
 
-// fill phase after a count phase that fell back to the exact kernels: reopen
-// the first-error word so the write pass can record it, and store the closing
-// offset (the reference's final push) the size query could not
-__global__ void reopen_kernel(uint64_t *res, uint64_t *offset, uint64_t cap_rows, const uint32_t *gate) {
-  if (*gate == 0) return;
-  if (res[8] == 0) res[8] = ~0ull;
-  if (offset && res[0] < cap_rows + 1) offset[res[0]] = res[1];
-}
-
 // label / weight columns: the single pass assumed one label (weight) entry per
 // row (and, for label column 0, a delimiter in every row); a nonzero check sum
 // hands the input to the exact kernels
@@ -117,7 +88,6 @@ __global__ void label_check_kernel(const uint64_t *labsum, uint32_t *gate) {
   }
   if (i == 0 && (a != 0 || b != 0 || c != 0)) *gate |= 1u;
 }
-
 
 }  // namespace
 
@@ -146,33 +116,7 @@ hipError_t launch_csv(const CsvArgs &a, const FastCsvArgs &f, bool use_fast, uin
     else launch_fast_tile<2>(f, sp, s);
     if (sp) label_check_kernel<<<1, kLabShards, 0, s>>>(f.labsum, gate);
   }
-  // ---- exact path, gated on the device flag (early exit when the fast path stood)
-  if (phase == kPhaseFill) reopen_kernel<<<1, 1, 0, s>>>(res, a.offset, a.cap[C_ROWS], gate);
-  const bool reset_tab = use_fast && phase != kPhaseCount && f.chunk_tab && f.nchunk > 0;
-  uint64_t *rtab = reset_tab ? f.chunk_tab : nullptr;
-  const uint64_t ntab = reset_tab ? (uint64_t)f.nchunk * 8 : 0;
-  if (a.ntiles) {
-    if (phase != kPhaseFill) {
-      csv_tile<1><<<a.ntiles, kThreads, 0, s>>>(a);
-      tile_scan_kernel<<<1, kThreads, 0, s>>>(a.tile_cnt, const_cast<uint64_t *>(a.tile_base), a.ntiles,
-                                              res, a.offset, a.cap[C_ROWS], gate, rtab, ntab, gate);
-      if (phase == kPhaseCount) note_gate_kernel<<<1, 1, 0, s>>>(gate);
-    } else {
-      // the count phase stood on the single-pass kernel but its write pass
-      // handed over: count on the exact path first (scan.h recount_flag_kernel)
-      recount_flag_kernel<<<1, 1, 0, s>>>(gate);
-      auto ra = a;
-      ra.gate = gate + 2;
-      csv_tile<1><<<a.ntiles, kThreads, 0, s>>>(ra);
-      tile_scan_kernel<<<1, kThreads, 0, s>>>(a.tile_cnt, const_cast<uint64_t *>(a.tile_base), a.ntiles,
-                                              res, a.offset, a.cap[C_ROWS], gate + 2, rtab, ntab, gate);
-    }
-    if (phase != kPhaseCount) {
-      if (!use_fast) prof_mark(0, s, "csv_tile<2>");
-      csv_tile<2><<<a.ntiles, kThreads, 0, s>>>(a);
-      if (!use_fast) prof_mark(1, s, "csv_tile<2>");
-    }
-  }
+  launch_exact_tail(csv_tile<1>, csv_tile<2>, a, a, f.chunk_tab, f.nchunk, res, gate, phase, use_fast, "csv_tile<2>", s);
   finish_kernel<<<1, 256, 0, s>>>(res, gate, f.err, phase != kPhaseCount ? f.chunk_tab : nullptr, f.nchunk);
   return hipGetLastError();
 }

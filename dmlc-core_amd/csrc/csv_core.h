@@ -360,11 +360,7 @@ DA_HDF void tile(const CsvArgs &a, Shared &sh, BK &bk, uint64_t k) {
   src.g = a.text;
   src.lds = sh.win;
   fast::init_dec_tables(sh.dt, bk);  // (read after the window's barrier)
-#ifdef FSVM_EXACT_BYTEDEC  // A/B only: the byte decoders everywhere
-  const fast::DecTables *dtp = nullptr;
-#else
   const fast::DecTables *dtp = &sh.dt;
-#endif
   while (!done) {
     uint64_t wend = mn(w0 + (uint64_t)kWin, a.n);
     if (wend == a.n) done = true;

@@ -306,13 +306,8 @@ DA_HDF void tile(const FastCsvArgs &a, Shared &sh, BK &bk, uint32_t k) {
   // the wait for it leaves them in flight (fast_common.h chunk_guess_begin)
   ChunkProbe cp;
   if (tid < kWave) cp = chunk_guess_begin(a.cs, a.nchunk, a.n, t.tlo, bk);
-#if defined(FSVM_GLDS) && defined(__HIP_DEVICE_COMPILE__)
-  constexpr bool kTextAfter = false;  // (the LDS-DMA form issues other loads: a full wait)
-  stage_issue_lds(a.text, a.n, t.tlo, sr, sh.c, bk);
-#else
   constexpr bool kTextAfter = true;  // stage_issue's kStageRounds loads follow the window load
   stage_issue(a.text, a.n, t.tlo, sr, bk);
-#endif
   // the tile's chunk list, made in the shadow of the text loads; its readers
   // come after the stage barrier
   if (tid < kWave) chunk_guess_end(a.cs, a.nchunk, t.tlo, t.thi, cp, kTextAfter && sr.interior, sh.c, bk);

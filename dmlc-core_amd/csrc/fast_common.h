@@ -232,55 +232,6 @@ DA_HD Masks classify64_lut(const uint8_t *p, const uint32_t *cls) {
   m.bad = (g & ~m.d) != 0;
   return m;
 }
-// ---- The same masks in registers (A/B build FSVM_REGCLS): eight one-bit
-// classes from two nibble tables by v_perm (digit, + - ., e E, ':', newline,
-// space, tab, and the letters a d i q t y, which qid_clean checks against
-// "qid:" as the table's N+C letters), then per plane a flag bit per byte
-// gathered four at a time by one multiply and shifted in by v_alignbit.
-constexpr uint32_t kRLoA = 0x01018121u, kRLoB = 0x01010581u, kRLoC = 0x0218C101u, kRLoD = 0x00021200u;
-constexpr uint32_t kRHiA = 0x09220050u, kRHiB = 0x80840004u;
-DA_HD uint32_t rcls4(uint32_t x) {  // one class bit per byte (0: outside the grammar)
-  const uint32_t s = x & 0x07070707u;
-  const uint32_t a = perm_b32(kRLoB, kRLoA, s), b = perm_b32(kRLoD, kRLoC, s);
-  const uint32_t m = perm_b32(0xFFFFFFFFu, 0u, (x >> 1) & 0x04040404u);  // 0xFF where the low nibble >= 8
-  const uint32_t hv = perm_b32(kRHiB, kRHiA, (x >> 4) & 0x07070707u);
-  return ((b & m) | (a & ~m)) & hv;
-}
-DA_HD uint32_t gather_in(uint32_t acc, uint32_t f, uint32_t mul) {  // acc << 4 | the 4 flags (one bit per byte)
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __builtin_amdgcn_alignbit(acc, f * mul, 28u);
-#else
-  return (acc << 4) | ((f * mul) >> 28);
-#endif
-}
-DA_HD Masks classify64_reg(const uint8_t *p) {
-  uint32_t d[2] = {0, 0}, g[2] = {0, 0}, n[2] = {0, 0}, c[2] = {0, 0};
-  uint32_t all = 0x80808080u, orv = 0;
-#pragma unroll
-  for (int q = 3; q >= 0; --q) {  // last dword first: each gather shifts the earlier ones up
-    uint32_t w[4];
-    load16(p + 16 * q, w);
-#pragma unroll
-    for (int j = 3; j >= 0; --j) {
-      const int h = q >> 1;
-      const uint32_t x = w[j], cls = rcls4(x);
-      all &= cls + 0x7F7F7F7Fu;
-      orv |= x;
-      g[h] = gather_in(g[h], cls & 0x01010101u, 0x10204080u);
-      d[h] = gather_in(d[h], ((cls & 0x07070707u) + 0x03030303u) & 0x04040404u, 0x04081020u);
-      n[h] = gather_in(n[h], ((cls & 0x90909090u) + 0x70707070u) & 0x80808080u, 0x00204081u);
-      c[h] = gather_in(c[h], ((cls & 0x88888888u) + 0x78787878u) & 0x80808080u, 0x00204081u);
-    }
-  }
-  Masks m;
-  m.d = d[0] | ((uint64_t)d[1] << 32);
-  m.g = g[0] | ((uint64_t)g[1] << 32);
-  m.n = n[0] | ((uint64_t)n[1] << 32);
-  m.c = c[0] | ((uint64_t)c[1] << 32);
-  m.hi = 0u;
-  m.bad = ((all & 0x80808080u) != 0x80808080u) || (orv & 0x80808080u);
-  return m;
-}
 
 // 4 bytes (x) through the table: 4-bit masks (a byte >= 0x80: r.hi, planes
 // cleared, bad; its table word is masked to the plane bits so that it cannot
@@ -613,37 +564,6 @@ DA_HD W16 win_at(const uint8_t *text, uint64_t tlo, uint64_t q) {
 
 // the same at tile offset o (position tlo + o)
 DA_HD W16 win_at_o(const uint8_t *text, uint32_t o) {
-#if defined(FSVM_UAWIN) && defined(__HIP_DEVICE_COMPILE__)
-  // one ds_read_b128 at the byte offset (gfx950 LDS takes unaligned reads)
-  uint4 v;
-  __builtin_memcpy(&v, text + o + kPre, 16);
-  W16 q;
-  q.lo = v.x | ((uint64_t)v.y << 32);
-  q.hi = v.z | ((uint64_t)v.w << 32);
-  return q;
-#endif
-#if defined(FSVM_WIN64)
-  {  // three 8-byte aligned reads (a wave's windows are ~16 B apart: b32 reads 4-way conflict)
-    const uint32_t off = o + kPre;
-    // (each address made opaque: merged into ds_read2_b64 the pair costs twice two ds_read_b64)
-    uint32_t a0 = off & ~7u, a1 = a0 + 8u, a2 = a0 + 16u;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" : "+v"(a1));
-    asm volatile("" : "+v"(a2));
-#endif
-    const uint64_t a = *reinterpret_cast<const uint64_t *>(text + a0), b = *reinterpret_cast<const uint64_t *>(text + a1),
-                   c = *reinterpret_cast<const uint64_t *>(text + a2);
-    const bool s = (off & 4u) != 0u;
-    const uint32_t x0 = s ? (uint32_t)(a >> 32) : (uint32_t)a, x1 = s ? (uint32_t)b : (uint32_t)(a >> 32),
-                   x2 = s ? (uint32_t)(b >> 32) : (uint32_t)b, x3 = s ? (uint32_t)c : (uint32_t)(b >> 32),
-                   x4 = s ? (uint32_t)(c >> 32) : (uint32_t)c;
-    const uint32_t sft = (off & 3u) * 8u;
-    W16 r;
-    r.lo = funnel(x1, x0, sft) | ((uint64_t)funnel(x2, x1, sft) << 32);
-    r.hi = funnel(x3, x2, sft) | ((uint64_t)funnel(x4, x3, sft) << 32);
-    return r;
-  }
-#endif
   const uint32_t off = o + kPre;
   const uint32_t *w = reinterpret_cast<const uint32_t *>(text + (off & ~3u));
   const uint32_t sft = (off & 3u) * 8u;
@@ -659,9 +579,6 @@ struct TileCommon {
   alignas(16) uint8_t text[kStage];  // position p <-> text[p - tlo + kPre]
   uint64_t csl[kMaxCs + 1];           // chunk starts in [tlo, thi]
   uint64_t cfloor, cnext, base[4];    // last chunk start <= tlo, first beyond the list, output bases
-#ifdef FSVM_LB_DRAIN
-  uint64_t lbw[4];                    // look-back: the inclusive prefix read by one lane
-#endif
   uint32_t ncs, c_first, toomany, bad;
 };
 
@@ -886,27 +803,6 @@ struct StageRegs {
   uint32_t w[kStageRounds][4];
   bool interior;
 };
-#if defined(FSVM_GLDS) && defined(__HIP_DEVICE_COMPILE__)
-// LDS-DMA form (global_load_lds_dwordx4): the staged range is contiguous in
-// HBM and in LDS, so each wave-instruction moves 1 KiB straight into LDS
-// (lane l's 16 bytes at base + 16 l) -- no staging VGPRs, no ds_write; the
-// barrier after stage_commit waits for them (vmcnt).  `c` names the LDS.
-constexpr int kStagePieces = (kStage + kWave * 16 - 1) / (kWave * 16);
-template <class BK>
-DA_HDF void stage_issue_lds(const uint8_t *text, uint64_t n, uint64_t tlo, StageRegs &r, TileCommon &c, BK &bk) {
-  r.interior = tlo >= (uint64_t)kPre && tlo + kTile + kPost <= n;
-  if (!r.interior) return;
-  const uint8_t *src = text + (tlo - kPre);
-  const int t = bk.tid(), lane = t & (kWave - 1), w = t / kWave;
-#pragma unroll
-  for (int q = w; q < kStagePieces; q += kFWaves) {
-    const int off = q * kWave * 16 + lane * 16;
-    if (off < kStage)
-      __builtin_amdgcn_global_load_lds((const void *)(src + off),
-                                       (__attribute__((address_space(3))) void *)(c.text + q * kWave * 16), 16, 0, 0);
-  }
-}
-#endif
 template <class BK>
 DA_HDF void stage_issue(const uint8_t *text, uint64_t n, uint64_t tlo, StageRegs &r, BK &bk) {
   r.interior = tlo >= (uint64_t)kPre && tlo + kTile + kPost <= n;
@@ -916,18 +812,7 @@ DA_HDF void stage_issue(const uint8_t *text, uint64_t n, uint64_t tlo, StageRegs
 #pragma unroll
   for (int i = 0; i < kStageRounds; ++i) {
     const int u = t + i * kFThreads;
-#if defined(FSVM_NT_STAGE) && defined(__HIP_DEVICE_COMPILE__)  // A/B: streaming (non-temporal) text loads
-    if (u < kStageUnits) {
-      typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-      const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(src + 16 * u));
-      r.w[i][0] = v.x;
-      r.w[i][1] = v.y;
-      r.w[i][2] = v.z;
-      r.w[i][3] = v.w;
-    }
-#else
     if (u < kStageUnits) load16(src + 16 * u, r.w[i]);
-#endif
   }
 }
 template <class BK>
@@ -937,10 +822,6 @@ DA_HDF void stage_commit(const uint8_t *text, uint64_t n, uint64_t tlo, const St
     stage(text, n, tlo, c, bk);
     return;
   }
-#if defined(FSVM_GLDS) && defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // stage_issue_lds's bytes have landed
-  return;
-#endif
   const int t = bk.tid();
 #pragma unroll
   for (int i = 0; i < kStageRounds; ++i) {
@@ -966,11 +847,6 @@ constexpr int kLbPer = FSVM_LB_PER;  // predecessors polled per lane per round
 DA_HD uint64_t pack4(const uint32_t c[4]) {
   return (uint64_t)c[0] | ((uint64_t)c[1] << 15) | ((uint64_t)c[2] << 30) | ((uint64_t)c[3] << 45);
 }
-DA_HD void drain_stores() {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-}
 
 // Inclusive prefixes are tagged words: incl[k][f] = kMark | value, each an
 // untorn 8-byte granule that the launch's memset left 0, so a reader takes
@@ -978,7 +854,6 @@ DA_HD void drain_stores() {
 // -- no drain between the prefix and a status flag, and the reader polls a
 // predecessor's status word and prefix words in the same round trip.
 constexpr uint64_t kMark = 1ull << 63;
-#ifndef FSVM_LB_DRAIN
 
 // Lane 0: publish this tile's aggregate (tile 0 publishes its inclusive).
 // kf / seed: a launch that resumes at tile kf (svm_lean.h) -- tile kf is the
@@ -1058,99 +933,6 @@ DA_HDF uint32_t look_back(uint64_t *lb, uint32_t ntiles, uint32_t k, const uint3
   }
   return rounds;
 }
-#else  // A/B build: inclusive prefix drained before an inclusive status word (round 2)
-// Lane 0: publish this tile's aggregate (tile 0 publishes its inclusive).
-DA_HD void publish_aggregate(uint64_t *lb, uint32_t ntiles, uint32_t k, const uint32_t cnt[4]) {
-  uint64_t *st = lb, *incl = lb + ntiles;
-  if (k == 0) {
-    for (int i = 0; i < 4; ++i) store_agent_u64(incl + i, cnt[i]);
-    drain_stores();
-    store_agent_u64(st, kSIncl | pack4(cnt));
-  } else {
-    store_agent_u64(st + k, kSAgg | pack4(cnt));
-  }
-}
-
-// Wave 0: decoupled look-back.  Poll i of lane l reads the status word of
-// predecessor j-1-(64 i + l) (each poll instruction reads 512 contiguous
-// bytes); a round consumes predecessors up to the first inclusive one and
-// stops before the first unpublished one.  cnt = this tile's counts (wave
-// uniform).  Ends with c.base[0..3] = exclusive prefixes, and publishes the
-// inclusive prefix.  Returns the number of rounds.  The caller synchronises.
-template <class BK>
-DA_HDF uint32_t look_back(uint64_t *lb, uint32_t ntiles, uint32_t k, const uint32_t cnt[4], uint32_t *gate,
-                          TileCommon &c, BK &bk) {
-  const uint32_t lane = bk.tid();
-  uint64_t *st = lb, *incl = lb + ntiles;
-  uint64_t j = k;
-  uint32_t spins = 0, rounds = 0;
-  uint64_t acc[4] = {0, 0, 0, 0};
-  bool done = k == 0;
-  while (!done) {
-    ++rounds;
-    uint64_t s[kLbPer];
-#pragma unroll
-    for (int i = 0; i < kLbPer; ++i) {
-      const uint64_t d = (uint64_t)i * kWave + lane;  // predecessor j-1-d
-      s[i] = d < j ? load_agent_u64(st + (j - 1 - d)) : kSIncl;  // before tile 0: an inclusive 0
-    }
-    // the nearest stop: the smallest d whose word is unpublished or inclusive
-    uint64_t D = (uint64_t)kWave * kLbPer;  // predecessors that contribute their aggregates
-    bool stop_incl = false;
-#pragma unroll
-    for (int i = kLbPer - 1; i >= 0; --i) {
-      const uint32_t state = (uint32_t)(s[i] >> 62);
-      const uint64_t mz = bk.ballot(state == 0), mi = bk.ballot(state == 2);
-      if (mz | mi) {
-        const uint32_t f = (uint32_t)ctz64(mz | mi);
-        D = (uint64_t)i * kWave + f;
-        stop_incl = (mi >> f) & 1u;
-      }
-    }
-    uint32_t part[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int i = 0; i < kLbPer; ++i) {
-      if ((uint64_t)i * kWave + lane < D) {
-#pragma unroll
-        for (int f = 0; f < 4; ++f) part[f] += (uint32_t)((s[i] >> (15 * f)) & 0x7FFFu);
-      }
-    }
-#pragma unroll
-    for (int f = 0; f < 4; ++f) acc[f] += bk.wave_sum(part[f]);
-    if (stop_incl) {
-      done = true;
-      if (D < j) {  // a real inclusive record (else: the start, 0)
-        if (lane < 4) c.lbw[lane] = load_agent_u64(incl + (j - 1 - D) * 4 + lane);
-        bk.wave_sync();
-#pragma unroll
-        for (int f = 0; f < 4; ++f) acc[f] += c.lbw[f];
-        bk.wave_sync();
-      }
-    } else {
-      j -= D;
-      if (D == 0) {
-        if (++spins > kSpinLimit) {  // never expected: hand the input to the exact path
-          if (lane == 0) atomic_or_u32(gate, 2u);
-          done = true;
-        }
-        spin_pause();
-      }
-    }
-  }
-  if (lane < 4) c.base[lane] = acc[lane == 0 ? 0 : lane == 1 ? 1 : lane == 2 ? 2 : 3];
-  if (k > 0) {
-    if (lane < 4) {
-      const uint64_t v = acc[lane == 0 ? 0 : lane == 1 ? 1 : lane == 2 ? 2 : 3];
-      const uint32_t cv = cnt[lane == 0 ? 0 : lane == 1 ? 1 : lane == 2 ? 2 : 3];
-      store_agent_u64(incl + (uint64_t)k * 4 + lane, v + cv);
-    }
-    drain_stores();
-    bk.wave_sync();
-    if (lane == 0) store_agent_u64(st + k, kSIncl | pack4(cnt));
-  }
-  return rounds;
-}
-#endif
 // words of look-back state per tile the launch must zero (status + prefix)
 constexpr uint64_t kLbWords = kFastLbWords;  // args.h: the launcher sizes the workspace by it
 

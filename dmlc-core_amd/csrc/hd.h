@@ -117,14 +117,6 @@ DA_HD void store_flag_u64(uint64_t *p, uint64_t v) {
 #endif
 }
 
-DA_HD uint32_t gridDim_x() {  // workgroups of the launch (0 on the host)
-#if defined(__HIP_DEVICE_COMPILE__)
-  return gridDim.x;
-#else
-  return 0;
-#endif
-}
-
 DA_HD uint32_t atomic_add_u32(uint32_t *p, uint32_t v) {  // returns the old value
 #if defined(__HIP_DEVICE_COMPILE__)
   return atomicAdd(p, v);

@@ -38,15 +38,6 @@ __global__ void __launch_bounds__(fast::kFThreads, FFM_MINW) fm_fast_tile(FastSv
   fsvm::tile<MODE, true>(a, sh, bk, blockIdx.x);
 }
 
-// fill phase after a count phase that fell back to the exact kernels: reopen
-// the first-error word and store the closing offset the size query could not
-__global__ void fm_reopen_kernel(uint64_t *res, uint64_t *offset, uint64_t cap_rows, const uint32_t *gate) {
-  if (*gate == 0) return;
-  if (res[8] == 0) res[8] = ~0ull;
-  if (offset && res[0] < cap_rows + 1) offset[res[0]] = res[1];
-}
-
-
 }  // namespace
 
 hipError_t launch_libfm(const LibfmArgs &a, const FastSvmArgs &f, bool use_fast, uint64_t *res, int phase,
@@ -71,40 +62,17 @@ hipError_t launch_libfm(const LibfmArgs &a, const FastSvmArgs &f, bool use_fast,
   if ((e = launch_prologue(fl, s)) != hipSuccess) return e;
   if (use_fast) {
     if (phase == kPhaseCount) {
-      fm_fast_tile<1><<<f.ntiles, fast::kFThreads, 0, s>>>(f);
+      fm_fast_tile<1><<<f.ntiles, fast::kFThreads, 0, s>>>(f);  // (unmarked, unlike the other two formats' count phase)
     } else {
       prof_mark(0, s, "fm_fast_tile<2>");
       fm_fast_tile<2><<<f.ntiles, fast::kFThreads, 0, s>>>(f);
       prof_mark(1, s, "fm_fast_tile<2>");
     }
   }
-  // ---- exact path, gated on the device flag (early exit when the fast path stood)
-  if (phase == kPhaseFill) fm_reopen_kernel<<<1, 1, 0, s>>>(res, a.offset, a.cap[C_ROWS], gate);
-  const bool reset_tab = use_fast && phase != kPhaseCount && a.chunk_tab && f.nchunk > 0;
-  uint64_t *rtab = reset_tab ? a.chunk_tab : nullptr;
-  const uint64_t ntab = reset_tab ? (uint64_t)f.nchunk * 8 : 0;
-  if (a.ntiles) {
-    if (phase != kPhaseFill) {
-      libfm_tile<1><<<a.ntiles, kThreads, 0, s>>>(a);
-      tile_scan_kernel<<<1, kThreads, 0, s>>>(a.tile_cnt, const_cast<uint64_t *>(a.tile_base), a.ntiles,
-                                              res, a.offset, a.cap[C_ROWS], gate, rtab, ntab, gate);
-      if (phase == kPhaseCount) note_gate_kernel<<<1, 1, 0, s>>>(gate);
-    } else {
-      // the count phase stood on the single-pass kernel but its write pass
-      // handed over: count on the exact path first (scan.h recount_flag_kernel)
-      recount_flag_kernel<<<1, 1, 0, s>>>(gate);
-      auto ra = a;
-      ra.gate = gate + 2;
-      libfm_tile<1><<<a.ntiles, kThreads, 0, s>>>(ra);
-      tile_scan_kernel<<<1, kThreads, 0, s>>>(a.tile_cnt, const_cast<uint64_t *>(a.tile_base), a.ntiles,
-                                              res, a.offset, a.cap[C_ROWS], gate + 2, rtab, ntab, gate);
-    }
-    if (phase != kPhaseCount) {
-      if (!use_fast) prof_mark(0, s, "libfm_tile<2>");
-      libfm_tile<2><<<a.ntiles, kThreads, 0, s>>>(a);
-      if (!use_fast) prof_mark(1, s, "libfm_tile<2>");
-    }
-  }
+  // (a.chunk_tab where the other two reset f.chunk_tab: never null -- the
+  // workspace's table when the caller gives none)
+  launch_exact_tail(libfm_tile<1>, libfm_tile<2>, a, a, a.chunk_tab, f.nchunk, res, gate, phase, use_fast,
+                    "libfm_tile<2>", s);
   finish_kernel<<<1, 256, 0, s>>>(res, gate, f.err, phase != kPhaseCount ? a.chunk_tab : nullptr, a.nchunk);
   if (use_fast && phase != kPhaseCount && f.indexing_mode < 0 &&
       (e = launch_umin_fix(f.index, f.field, f.wide, f.chunk_tab, f.nchunk, f.umin, res, gate, f.cap[C_INDEX], f.cap[C_FIELD], s)) !=

@@ -308,11 +308,7 @@ DA_HDF void tile(const LibfmArgs &a, svm::Shared &sh, BK &bk, uint64_t k) {
   }
   if (tid == 0) sh.pending[1] = kNone;
   fast::init_dec_tables(sh.dt, bk);
-#ifdef FSVM_EXACT_BYTEDEC  // A/B only: the byte decoders everywhere
-  const fast::DecTables *dtp = nullptr;
-#else
   const fast::DecTables *dtp = &sh.dt;
-#endif
   bk.sync();
   int j = 0;             // window counter
   uint32_t st0 = S_PRE;  // concrete state at the window start

@@ -5,8 +5,6 @@
 //                   the grammar
 //   libsvm_tile     exact count / write tile kernels (libsvm_core.h), run
 //                   only when the gate is set (or indexing_mode < 0)
-#include <atomic>
-
 #include "block.h"
 #include "dmlc_amd_kernels.h"
 #include "libsvm_core.h"
@@ -54,32 +52,11 @@ template <int MODE>
 #ifndef FSVM_MINW
 #define FSVM_MINW (fast::kFWaves == 1 ? 5 : 6)  // waves per SIMD the fill kernel is register-budgeted for
 #endif
-#ifndef FSVM_PERSIST
-#define FSVM_PERSIST 0  // workgroups loop over tiles (svm_fast.h tile_p)
-#endif
 __global__ void __launch_bounds__(fast::kFThreads, FSVM_MINW) svm_fast_tile(FastSvmArgs a) {
   __shared__ __attribute__((aligned(16))) fsvm::Shared sh;
   __shared__ uint64_t scratch[kSmallScratchU64];
-#ifdef FSVM_ABL_PAD_LDS  // occupancy experiment only: pad the workgroup's LDS
-  __shared__ uint32_t pad[FSVM_ABL_PAD_LDS / 4];
-  if (a.n == 1) pad[threadIdx.x] = 1, a.res[15] = pad[(threadIdx.x + 1) % fast::kFThreads];
-#endif
   DevBlockS bk{scratch};
-#if FSVM_PERSIST
-  // persistent: the first tile is the workgroup's index (dispatch order makes
-  // every lower one resident first), later ones come from the ticket
-  if (a.skip_if_gated && *a.gate) return;  // fill phase after an exact-path count: block-uniform
-  fsvm::init_tables(sh, bk);
-  fast::StageRegs sr;
-  uint32_t k = blockIdx.x;
-  fast::stage_issue(a.text, a.n, (uint64_t)k * fast::kTile, sr, bk);
-  while (k < a.ntiles) {
-    k = fsvm::tile_p<MODE, false, true>(a, sh, bk, k, sr);
-    bk.sync();  // every thread is done with the tile's LDS
-  }
-#else
   fsvm::tile<MODE>(a, sh, bk, blockIdx.x);
-#endif
 }
 
 // The lean single-pass kernel (svm_lean.h), ahead of svm_fast_tile<2> in a
@@ -106,42 +83,6 @@ bool lean_enabled() {
   return on != 0;
 }
 
-// workgroups of a persistent single-pass launch: what the device holds at
-// once (the occupancy calculator, capped at the 6 per CU the LDS budget
-// allows), never more than the tiles.  The per-device answer is cached in
-// atomics: the engine's workers launch from several host threads.  (The
-// persistent form -- FSVM_PERSIST, off by default -- takes later tiles from a
-// ticket, so it never deadlocks; when other streams' kernels share the device
-// and part of the grid is not resident, the look-back's kSpinLimit valve is
-// what bounds a wait on a tile that is not yet running.)
-template <class K>
-uint32_t persistent_grid(K kernel, uint32_t ntiles) {
-  static std::atomic<int> cache_n[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return ntiles;
-  int n = cache_n[dev].load(std::memory_order_relaxed);
-  if (n == 0) {
-    int cus = 0, per = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, fast::kFThreads, 0) != hipSuccess || cus < 1 || per < 1)
-      return ntiles;
-    const int cap = 6 * kWaves / fast::kFWaves;
-    n = cus * (per < cap ? per : cap);
-    cache_n[dev].store(n, std::memory_order_relaxed);
-  }
-  return (uint32_t)n < ntiles ? (uint32_t)n : ntiles;
-}
-
-// fill phase after a count phase that fell back to the exact kernels: the
-// count phase's select turned "no error" (~0) into 0; reopen it so the write
-// pass can record the first error, and store the closing offset (the
-// reference's final push, libsvm_parser.h:157-159) the size query could not
-__global__ void reopen_kernel(uint64_t *res, uint64_t *offset, uint64_t cap_rows, const uint32_t *gate) {
-  if (*gate == 0) return;
-  if (res[8] == 0) res[8] = ~0ull;
-  if (offset && res[0] < cap_rows + 1) offset[res[0]] = res[1];
-}
-
 // after the single-pass kernel: the tiles' qid run counts against the rows
 // (svm_fast.h qid_decide); when every row has a qid, each chunk row's qid
 // count is its row count
@@ -160,7 +101,6 @@ __global__ void __launch_bounds__(256) qid_fix_kernel(const uint64_t *qsum, uint
       if (row[C_ROWS] != ~0ull) row[C_QID] = row[C_ROWS];
     }
 }
-
 
 }  // namespace
 
@@ -185,7 +125,7 @@ hipError_t launch_libsvm(const LibsvmArgs &a, const FastSvmArgs &f, bool use_fas
   const bool lean = use_fast && phase == kPhaseFull && f.indexing_mode >= 0 && f.lean_lb && lean_enabled();
   if (lean) fl.add(f.lean_lb, (uint64_t)f.ntiles * fast::kLbWords + 1, 0);  // + the poison word
   if (use_fast) {
-    fl.add(f.lb, (uint64_t)f.ntiles * fast::kLbWords + 1, 0);  // + the ticket word
+    fl.add(f.lb, (uint64_t)f.ntiles * fast::kLbWords + 1, 0);  // + a reserved word
     fl.add(f.qsum, kLabShards * 8, 0);
     if (phase != kPhaseCount && f.indexing_mode < 0) fl.add(f.umin, (uint64_t)f.nchunk, ~0ull);
   }
@@ -197,7 +137,7 @@ hipError_t launch_libsvm(const LibsvmArgs &a, const FastSvmArgs &f, bool use_fas
   if (use_fast) {
     if (phase == kPhaseCount) {
       prof_mark(0, s, "svm_fast_tile<1>");
-      svm_fast_tile<1><<<FSVM_PERSIST ? persistent_grid(svm_fast_tile<1>, f.ntiles) : f.ntiles, fast::kFThreads, 0, s>>>(fa);
+      svm_fast_tile<1><<<f.ntiles, fast::kFThreads, 0, s>>>(fa);
       prof_mark(1, s, "svm_fast_tile<1>");
     } else if (lean) {
       // the full kernel resumes at the first tile the lean one poisoned (all
@@ -205,10 +145,10 @@ hipError_t launch_libsvm(const LibsvmArgs &a, const FastSvmArgs &f, bool use_fas
       prof_mark(0, s, "svm_lean_tile");
       svm_lean_tile<<<f.ntiles, fast::kFThreads, 0, s>>>(f);
       prof_mark(1, s, "svm_lean_tile");
-      svm_fast_tile<2><<<f.ntiles, fast::kFThreads, 0, s>>>(f);
+      svm_fast_tile<2><<<f.ntiles, fast::kFThreads, 0, s>>>(f);  // (unmarked: the profile names the lean kernel)
     } else {
       prof_mark(0, s, "svm_fast_tile<2>");
-      svm_fast_tile<2><<<FSVM_PERSIST ? persistent_grid(svm_fast_tile<2>, f.ntiles) : f.ntiles, fast::kFThreads, 0, s>>>(fa);
+      svm_fast_tile<2><<<f.ntiles, fast::kFThreads, 0, s>>>(fa);
       prof_mark(1, s, "svm_fast_tile<2>");
     }
     // the qid decision (qid_fix_kernel) is folded into the exact count
@@ -221,34 +161,8 @@ hipError_t launch_libsvm(const LibsvmArgs &a, const FastSvmArgs &f, bool use_fas
     ac.qsum = f.qsum;
     ac.qres = res;
   }
-  // ---- exact path, gated on the device flag (early exit when the fast path stood)
-  if (phase == kPhaseFill) reopen_kernel<<<1, 1, 0, s>>>(res, a.offset, a.cap[C_ROWS], gate);
-  // the chunk rows the single pass wrote are reset when it handed over
-  const bool reset_tab = use_fast && phase != kPhaseCount && f.chunk_tab && f.nchunk > 0;
-  uint64_t *rtab = reset_tab ? f.chunk_tab : nullptr;
-  const uint64_t ntab = reset_tab ? (uint64_t)f.nchunk * 8 : 0;
-  if (a.ntiles) {
-    if (phase != kPhaseFill) {
-      libsvm_tile<1><<<a.ntiles, kThreads, 0, s>>>(ac);
-      tile_scan_kernel<<<1, kThreads, 0, s>>>(a.tile_cnt, const_cast<uint64_t *>(a.tile_base), a.ntiles,
-                                              res, a.offset, a.cap[C_ROWS], gate, rtab, ntab, gate);
-      if (phase == kPhaseCount) note_gate_kernel<<<1, 1, 0, s>>>(gate);
-    } else {
-      // the count phase stood on the single-pass kernel but its write pass
-      // handed over: count on the exact path first (scan.h recount_flag_kernel)
-      recount_flag_kernel<<<1, 1, 0, s>>>(gate);
-      auto ra = a;
-      ra.gate = gate + 2;
-      libsvm_tile<1><<<a.ntiles, kThreads, 0, s>>>(ra);
-      tile_scan_kernel<<<1, kThreads, 0, s>>>(a.tile_cnt, const_cast<uint64_t *>(a.tile_base), a.ntiles,
-                                              res, a.offset, a.cap[C_ROWS], gate + 2, rtab, ntab, gate);
-    }
-    if (phase != kPhaseCount) {
-      if (!use_fast) prof_mark(0, s, "libsvm_tile<2>");
-      libsvm_tile<2><<<a.ntiles, kThreads, 0, s>>>(a);
-      if (!use_fast) prof_mark(1, s, "libsvm_tile<2>");
-    }
-  }
+  launch_exact_tail(libsvm_tile<1>, libsvm_tile<2>, a, ac, f.chunk_tab, f.nchunk, res, gate, phase, use_fast,
+                    "libsvm_tile<2>", s);
   finish_kernel<<<1, 256, 0, s>>>(res, gate, f.err, phase != kPhaseCount ? f.chunk_tab : nullptr, f.nchunk,
                                   use_fast && phase != kPhaseFill ? f.qsum : nullptr);
   if (use_fast && phase != kPhaseCount && f.indexing_mode < 0 &&

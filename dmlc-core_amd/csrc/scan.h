@@ -2,6 +2,7 @@
 // pipeline finalisation.  Included by each kernel translation unit (no RDC).
 #pragma once
 #include "block.h"
+#include "dmlc_amd_kernels.h"
 
 namespace dmlc_amd {
 namespace {  // one private copy per kernel translation unit (no RDC)
@@ -88,6 +89,55 @@ __device__ __forceinline__ void chunk_fixup_body(uint64_t *chunk_tab, int nchunk
 // first.  gate[1] = the gate as the count phase left it; gate[2] = "recount".
 __global__ void note_gate_kernel(uint32_t *gate) { gate[1] = gate[0]; }
 __global__ void recount_flag_kernel(uint32_t *gate) { gate[2] = (gate[0] != 0 && gate[1] == 0) ? 1u : 0u; }
+
+// fill phase after a count phase that fell back to the exact kernels: the
+// count phase's select turned "no error" (~0) into 0; reopen it so the write
+// pass can record the first error, and store the closing offset (the
+// reference's final push, libsvm_parser.h:157-159) the size query could not
+__global__ void reopen_kernel(uint64_t *res, uint64_t *offset, uint64_t cap_rows, const uint32_t *gate) {
+  if (*gate == 0) return;
+  if (res[8] == 0) res[8] = ~0ull;
+  if (offset && res[0] < cap_rows + 1) offset[res[0]] = res[1];
+}
+
+// ---- the exact path of a call, after its single-pass launches and before
+// finish_kernel: the same for the three text formats.  Every kernel is gated
+// on the device flag (early exit when the single pass stood).  count_k /
+// write_k: the format's exact tile kernels <1> / <2>; a: their arguments; ac:
+// the count pass's of a full / count phase (libsvm adds its qid check, else
+// a); tab, nchunk: the chunk rows the single pass wrote, reset when it handed
+// over; write_name: write_k's profile mark (only when no single pass ran
+// ahead of it, which then carries the marks).
+template <class A>
+void launch_exact_tail(void (*count_k)(A), void (*write_k)(A), const A &a, const A &ac, uint64_t *tab, int nchunk,
+                       uint64_t *res, uint32_t *gate, int phase, bool use_fast, const char *write_name,
+                       hipStream_t s) {
+  if (phase == kPhaseFill) reopen_kernel<<<1, 1, 0, s>>>(res, a.offset, a.cap[C_ROWS], gate);
+  const bool reset_tab = use_fast && phase != kPhaseCount && tab && nchunk > 0;
+  uint64_t *rtab = reset_tab ? tab : nullptr;
+  const uint64_t ntab = reset_tab ? (uint64_t)nchunk * 8 : 0;
+  if (!a.ntiles) return;
+  if (phase != kPhaseFill) {
+    count_k<<<a.ntiles, kThreads, 0, s>>>(ac);
+    tile_scan_kernel<<<1, kThreads, 0, s>>>(a.tile_cnt, const_cast<uint64_t *>(a.tile_base), a.ntiles, res,
+                                            a.offset, a.cap[C_ROWS], gate, rtab, ntab, gate);
+    if (phase == kPhaseCount) note_gate_kernel<<<1, 1, 0, s>>>(gate);
+  } else {
+    // the count phase stood on the single-pass kernel but its write pass
+    // handed over: count on the exact path first (recount_flag_kernel)
+    recount_flag_kernel<<<1, 1, 0, s>>>(gate);
+    A ra = a;
+    ra.gate = gate + 2;
+    count_k<<<a.ntiles, kThreads, 0, s>>>(ra);
+    tile_scan_kernel<<<1, kThreads, 0, s>>>(a.tile_cnt, const_cast<uint64_t *>(a.tile_base), a.ntiles, res,
+                                            a.offset, a.cap[C_ROWS], gate + 2, rtab, ntab, gate);
+  }
+  if (phase != kPhaseCount) {
+    if (!use_fast) prof_mark(0, s, write_name);
+    write_k<<<a.ntiles, kThreads, 0, s>>>(a);
+    if (!use_fast) prof_mark(1, s, write_name);
+  }
+}
 
 // ---- per-call set-up and finish, one launch each (every kernel boundary on
 // the stream costs a few microseconds: the set-up used to be six memsets and

@@ -170,7 +170,7 @@ struct Shared {  // LDS of one workgroup
   uint64_t prebad;            // pre-halo bytes outside the grammar (dirty_lines)
   uint64_t qfail[kFWaves];    // segments whose first-pass "qid:" check failed (the comment pass's plane path)
   uint32_t npass;
-  uint32_t next;   // persistent form: the next tile id
+  uint32_t reserved;  // unused (without it the LDS offsets move, and the kernels' schedule with them)
   uint32_t nq;     // qid runs of the tile
   uint32_t hashy;  // a byte outside the grammar: comments to blank (pass 1)
   uint32_t ndl, ndr, dgate, nseg;
@@ -574,12 +574,7 @@ DA_HDF uint32_t comment_erase(uint64_t tlo, uint64_t thi, uint64_t n, TileCommon
   // caller clears the bits) instead of being classified again: its planes
   // are exactly the reclassified ones (the comment bytes read as blanks,
   // the rest as classified -- a qid token next to a comment fails the check)
-#ifndef FSVM_CMT_BLANK  // A/B: every comment blanked and reclassified
   const bool via_planes = M != 0 && planes_ok;
-#else
-  const bool via_planes = false;
-  (void)planes_ok;
-#endif
   *Mplanes = via_planes ? M : 0;
   for (uint64_t m = bk.ballot(M != 0); m; m &= m - 1) {  // wave-uniform
     const uint32_t s = (uint32_t)ctz64(m);
@@ -918,20 +913,15 @@ DA_HD SegOutFm segment_roles_fm(const Tile &t, int tid) {
 // The exact byte decoders: rare on this path (exponents, runs that may cross
 // the 16-byte window or a chunk end, 9+ digit indices).
 // (Measured: out of line they cost more than the code size saves, so they
-// stay inline unless FSVM_OUTLINE_SLOW is defined.)
-#if defined(FSVM_OUTLINE_SLOW) && defined(__HIP_DEVICE_COMPILE__)
-#define FSVM_COLD __device__ __attribute__((noinline))
-#else
-#define FSVM_COLD DA_HD
-#endif
+// stay inline.)
 // They read the text from global memory: no LDS pointer crosses the call.
-FSVM_COLD float slow_float(const uint8_t *text, uint64_t q, uint64_t lim) {
+DA_HD float slow_float(const uint8_t *text, uint64_t q, uint64_t lim) {
   GSrc src{text, lim};
   uint64_t e;
   bool nan_err = false;
   return parse_float(src, q, &e, &nan_err);
 }
-FSVM_COLD bool slow_uint(const uint8_t *text, uint64_t q, uint64_t lim, int wide, uint64_t *v) {
+DA_HD bool slow_uint(const uint8_t *text, uint64_t q, uint64_t lim, int wide, uint64_t *v) {
   GSrc src{text, lim};
   return parse_uint(src, q, wide != 0, v);
 }
@@ -986,11 +976,7 @@ DA_HDF uint32_t commit_seg(const Tile &t, Shared &sh, int seg, At at, bool first
 template <bool FM, class At>
 DA_HDF uint32_t classify_tile(const Tile &t, Shared &sh, int tid, At at, bool first, uint32_t parts) {
   uint32_t bad = 0;
-#ifdef FSVM_REGCLS  // A/B: the segment's classes in registers (fast_common.h classify64_reg)
-  if (parts & 1u) bad = commit_seg<FM>(t, sh, tid, at, first, classify64_reg(sh.c.text + kPre + tid * kSegB));
-#else
   if (parts & 1u) bad = commit_seg<FM>(t, sh, tid, at, first, classify64_lut(sh.c.text + kPre + tid * kSegB, sh.cls));
-#endif
   if ((parts & 4u) && tid == kPostLane) {  // digits of the 16 bytes after the tile (windows of my last runs)
     uint32_t g = 0;
 #pragma unroll
@@ -1026,14 +1012,10 @@ DA_HDF uint32_t classify_tile(const Tile &t, Shared &sh, int tid, At at, bool fi
   return bad;
 }
 
-// CSR stores (A/B FSVM_NT_STORE: non-temporal -- the outputs are written once)
+// CSR stores
 template <class T>
 DA_HD void out_store(T *p, T v) {
-#if defined(FSVM_NT_STORE) && defined(__HIP_DEVICE_COMPILE__)
-  __builtin_nontemporal_store(v, p);
-#else
   *p = v;
-#endif
 }
 
 // ---- per-line fallback.  A line holding bytes outside the grammar (after
@@ -1631,17 +1613,8 @@ DA_HDF void init_tables(Shared &sh, BK &bk) {
 }
 
 // MODE 1: count only (size query); MODE 2: parse and write.
-//
-// PERSIST (the kernel's workgroups loop over tiles, svm_fast_tile): `sr`
-// already holds tile k's staged loads and the tables are in place; the tile
-// takes the next tile id from the launch's ticket early on (one returning
-// atomic, its latency hidden behind the tile's work) and issues that tile's
-// loads into `sr` once its own register batch is stored, so the next tile's
-// HBM latency overlaps this tile's stores.  Returns the next tile id (block
-// uniform).  Deadlock-free in any residency: a tile id is handed out only to
-// a resident workgroup, after every lower id was.
-template <int MODE, bool FM = false, bool PERSIST = false, class BK>
-DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, StageRegs &sr) {
+template <int MODE, bool FM = false, class BK>
+DA_HDF void tile_body(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k) {
   // Tile k = workgroup k (its blockIdx).  The look-back needs every tile's
   // predecessors to become resident eventually; workgroups are dispatched in
   // index order on every XCD, so the least unstarted tile's XCD only holds
@@ -1650,16 +1623,16 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
   // capped the 131k-tile launch at ~1.5 ms.)  Should a predecessor ever not
   // publish, kSpinLimit bounds the wait and the exact kernels take over.
   const int tid = bk.tid();
-  if (!PERSIST && a.skip_if_gated && *a.gate) return a.ntiles;  // fill phase after an exact-path count: block-uniform
+  if (a.skip_if_gated && *a.gate) return;  // fill phase after an exact-path count: block-uniform
   // after the lean kernel (svm_lean.h): resume at its first poisoned tile kf
   // (the word holds ~kf; 0: none poisoned, nothing left to do), tile kf's
   // exclusive prefix seeded by the lean inclusive prefix of tile kf - 1
   uint32_t kf = 0;
   const uint64_t *seed = nullptr;  // tile kf's exclusive prefix: the lean inclusive words of kf - 1 (marked)
-  if (!PERSIST && a.lean_poison) {
+  if (a.lean_poison) {
     const uint64_t pw = *a.lean_poison;  // stable: the lean launch has finished
     kf = pw ? (uint32_t)mn<uint64_t>(~pw, (uint64_t)a.ntiles) : a.ntiles;
-    if (k < kf) return a.ntiles;  // block-uniform
+    if (k < kf) return;  // block-uniform
     if (k == kf && kf > 0) seed = a.lean_lb + (uint64_t)a.ntiles + (uint64_t)(kf - 1) * 4;
   }
   FAST_STAMP(k, 0);
@@ -1669,29 +1642,15 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
   t.sh = &sh;
   t.tlo = (uint64_t)k * kTile;
   t.thi = mn<uint64_t>(t.tlo + kTile, a.n);
-  uint32_t knext = a.ntiles;  // thread 0: the ticket's answer (PERSIST)
-  if (PERSIST && tid == 0) knext = gridDim_x() + atomic_add_u32(a.ticket, 1u);
   // wave 0: the window of unit starts, issued ahead of the text loads so that
   // the wait for it leaves them in flight (fast_common.h chunk_guess_begin)
   ChunkProbe cp;
   if (tid < kWave) cp = chunk_guess_begin(a.cs, a.nchunk, a.n, t.tlo, bk);
-#if defined(FSVM_GLDS) && defined(__HIP_DEVICE_COMPILE__)
-  constexpr bool kTextAfter = false;  // (the LDS-DMA form issues other loads: a full wait)
-  if (!PERSIST) stage_issue_lds(a.text, a.n, t.tlo, sr, sh.c, bk);
-#else
-  constexpr bool kTextAfter = !PERSIST;  // stage_issue's kStageRounds loads follow the window load
-  if (!PERSIST) stage_issue(a.text, a.n, t.tlo, sr, bk);
-#endif
-#ifdef FSVM_PF_AHEAD  // A/B: touch tile k + FSVM_PF_AHEAD (same XCD) so its staging hits L2 / MALL
-  uint32_t pfv = 0;
-  {
-    const uint64_t pk = (uint64_t)k + FSVM_PF_AHEAD, off = pk * kTile + (uint64_t)tid * kSegB;
-    if (pk < a.ntiles && off < a.n) pfv = a.text[off];
-  }
-#endif
+  StageRegs sr;
+  stage_issue(a.text, a.n, t.tlo, sr, bk);  // its kStageRounds loads follow the window load
   // the tile's chunk list, made in the shadow of the text loads; its readers
   // come after the stage barrier
-  if (tid < kWave) chunk_guess_end(a.cs, a.nchunk, t.tlo, t.thi, cp, kTextAfter && sr.interior, sh.c, bk);
+  if (tid < kWave) chunk_guess_end(a.cs, a.nchunk, t.tlo, t.thi, cp, sr.interior, sh.c, bk);
   FAST_STAMP(k, 11);
   if (tid == 0) {
     sh.u.m.d[0] = sh.u.m.n[0] = sh.u.m.c[0] = 0;
@@ -1701,15 +1660,11 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
     sh.prebad = 0;
     sh.ndl = sh.ndr = sh.nseg = sh.dgate = 0;
   }
-  if (!PERSIST) init_tables(sh, bk);
+  init_tables(sh, bk);
   stage_commit(a.text, a.n, t.tlo, sr, sh.c, bk);
   FAST_STAMP(k, 10);  // wave 0 is at the stage barrier: its own text has landed and is stored
   bk.sync();
   FAST_STAMP(k, 2);
-#if defined(FSVM_ABL_STOP) && FSVM_ABL_STOP == 0  // timing ablation only: stage
-  if (sh.c.text[tid] == 0xAB && sh.c.ncs == 7) a.res[15] = sh.c.cnext;
-  return a.ntiles;
-#endif
   // ---- classify: segment tid -> slot tid+1; lanes 0..15 also one word each
   // of the 64 bytes before the tile -> slot 0
   // a text byte (0 outside the text) for the qid token checks: staged, or
@@ -1724,11 +1679,9 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
   // a byte outside the grammar ('#' among them) in the tile or in the pre-halo:
   // blank the comments and classify again (block-uniform, libsvm only)
   if (!FM && __builtin_expect(sh.hashy != 0, 0)) {
-#ifndef FSVM_NO_PRIO
     // until its aggregate is published, this tile holds up every later
-    // tile's look-back: its waves go first (A/B: FSVM_NO_PRIO)
+    // tile's look-back: its waves go first
     prio_high();
-#endif
     // The comment pass first, unless at most two segments (the pre-halo
     // counting as one) hold bytes outside the grammar and every '#' among
     // them opens a line (only blanks back to a newline: no comment to the
@@ -1772,10 +1725,6 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
   }
   if (tid == 0) bad |= sh.c.toomany;
   FAST_STAMP(k, 3);
-#if defined(FSVM_ABL_STOP) && FSVM_ABL_STOP == 1  // timing ablation only: stage + classify
-  if (sh.u.m.d[tid + 1] == 0x123456789ull) a.res[15] = sh.u.m.n[tid];
-  return a.ntiles;
-#endif
   // ---- roles, counts, eligibility
   SegOut so;
   so.Q = 0;
@@ -1799,23 +1748,11 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
   const uint64_t mine = (uint64_t)popc64(so.L) | ((uint64_t)popc64(so.W) << 16) |
                         ((uint64_t)popc64(so.I) << 32) | ((uint64_t)popc64(so.V) << 48);
   uint64_t totp;
-#ifdef FSVM_DPP_SCAN
-  const uint64_t ex = bk.exclusive_add(mine, &totp);
-#elif defined(FSVM_SCAN1) && defined(__HIP_DEVICE_COMPILE__)
-  const uint64_t ex = bk.exclusive1(mine, (uint64_t)0, AddU64(), &totp);
-#else
   const uint64_t ex = bk.exclusive(mine, (uint64_t)0, AddU64(), &totp);
-#endif
   FAST_STAMP(k, 4);
   const uint32_t nL = (uint32_t)(totp & 0xFFFF), nW = (uint32_t)((totp >> 16) & 0xFFFF),
                  nI = (uint32_t)((totp >> 32) & 0xFFFF), nV = (uint32_t)(totp >> 48);
-#if defined(FSVM_ABL_STOP) && FSVM_ABL_STOP == 2  // + roles + block scan
-  if (ex == 0x123456789ull) a.res[15] = totp;
-  return a.ntiles;
-#endif
-#ifndef FSVM_NO_PRIO
   if (!FM) prio_normal();  // (every wave resets its own; one scalar instruction, no LDS read)
-#endif
   // ---- publish this tile's aggregate
   const uint32_t cnt4[4] = {nL, nI, nV, nW};  // look-back slots Q_ROWS, Q_INDEX, Q_VALUE, Q_WEIGHT
   if (tid == 0) {
@@ -1837,11 +1774,6 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
   auto lim_of = [&](uint64_t q) { return one_chunk ? sh.c.cnext : t.next_cs(q); };
   // non-digit flags of the 16 window bytes at tile offset o (bits 16+ unused)
   auto ndig_at = [&](uint32_t o) -> uint32_t {
-#if defined(FSVM_UAWIN) && defined(__HIP_DEVICE_COMPILE__)
-    uint32_t x;  // the plane bytes from o / 8 on: one unaligned ds_read_b32
-    __builtin_memcpy(&x, reinterpret_cast<const uint8_t *>(sh.gw) + (o >> 3), 4);
-    return ~(x >> (o & 7u));
-#endif
     const uint32_t i = o >> 5;
     return ~funnel(sh.gw[i + 1], sh.gw[i], o & 31u);
   };
@@ -1858,10 +1790,6 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
     return false;
   };
   auto win_float = [&](uint32_t o, bool *ok) -> float {
-#ifdef FSVM_ABL_NODEC  // timing ablation only (tools/build_variants.sh), never shipped
-    *ok = true;
-    return (float)o;
-#endif
     const W16 wq = win_at_o(sh.c.text, o);
     const uint32_t w4[4] = {(uint32_t)wq.lo, (uint32_t)(wq.lo >> 32), (uint32_t)wq.hi, (uint32_t)(wq.hi >> 32)};
     bool k1;
@@ -1872,10 +1800,6 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
   // the id as read (<= 8 digits: 32 bits); ids_of applies indexing_mode > 0
   // in the index width
   auto win_index = [&](uint32_t o, bool *ok) -> uint32_t {
-#ifdef FSVM_ABL_NODEC
-    *ok = true;
-    return o;
-#endif
     const W16 wq = win_at_o(sh.c.text, o);
     const uint32_t w4[4] = {(uint32_t)wq.lo, (uint32_t)(wq.lo >> 32), (uint32_t)wq.hi, (uint32_t)(wq.hi >> 32)};
     uint64_t v;
@@ -1983,24 +1907,9 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
     FAST_STAMP(k, 6);
   }
   // ---- decoupled look-back by wave 0 (fast_common.h)
-#ifdef FSVM_ABL_NOLB  // timing ablation only: write pass without look-back (bases k * counts, in bounds)
-  if (MODE == 2 && tid < 4) {
-    const int slot = tid == Q_ROWS ? C_ROWS : tid == Q_INDEX ? C_INDEX : tid == Q_VALUE ? C_VALUE : C_WEIGHT;
-    const uint64_t c = cnt4[tid], cap = a.cap[slot];
-    sh.c.base[tid] = cap > c + 64 ? mn<uint64_t>((uint64_t)k * c, cap - c - 64) : 0;
-  }
-  if (MODE != 2 && tid < kWave) {
-#else
   if (tid < kWave) {
-#endif
-#ifdef FSVM_LB_PRIO  // A/B: the look-back wave ahead of the other tiles' waves
-    prio_high();
-#endif
     const uint32_t rounds =
         look_back(a.lb, a.ntiles, k, cnt4, a.gate, sh.c, bk, kf, seed);
-#ifdef FSVM_LB_PRIO
-    prio_normal();
-#endif
 #if defined(DMLC_AMD_STAMPS) && defined(__HIP_DEVICE_COMPILE__)
     if (tid == 0 && k < kStampTiles) g_stamps[(uint64_t)k * kStampSlots + 15] = rounds;
 #else
@@ -2010,14 +1919,8 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
     if (MODE == 2 && k == 1 && tid == 0) atomic_or_u32(a.gate, 2u);
 #endif
   }
-  if (PERSIST && tid == 0) sh.next = knext;
   bk.sync();
   FAST_STAMP(k, 7);
-  const uint32_t kn = PERSIST ? sh.next : a.ntiles;
-#if defined(FSVM_ABL_STOP) && FSVM_ABL_STOP == 3  // + first decode batch + look-back
-  if (sh.c.base[0] == 0x123456789ull) a.res[15] = (uint64_t)ib[0] + (uint64_t)fb[0];
-  return a.ntiles;
-#endif
   const uint64_t bRows = sh.c.base[Q_ROWS], bIdx = sh.c.base[Q_INDEX], bVal = sh.c.base[Q_VALUE],
                  bW = sh.c.base[Q_WEIGHT];
   // ---- the last tile publishes the totals (dmlc_amd_result.count)
@@ -2032,10 +1935,7 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
     a.res[C_FIELD] = FM ? bIdx + nI : 0;
     if (MODE == 2 && a.offset && rows < a.cap[C_ROWS] + 1) a.offset[rows] = bIdx + nI;
   }
-  if (MODE != 2) {
-    if (PERSIST && kn < a.ntiles) stage_issue(a.text, a.n, (uint64_t)kn * kTile, sr, bk);
-    return kn;
-  }
+  if (MODE != 2) return;
 
   // ---- stores
   const uint64_t eL = bRows + fL(ex), eW = bW + fW(ex), eI = bIdx + fI(ex), eV = bVal + fV(ex);
@@ -2057,23 +1957,8 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
       store_flag_u64(&a.umin[u], 0);
     }
   };
-#ifdef FSVM_INB  // A/B: every store of the tile in bounds (block-uniform): no per-store capacity branch
-  const bool inb = bRows + nL <= a.cap[C_ROWS] && bIdx + nI <= a.cap[C_INDEX] && bVal + nV <= a.cap[C_VALUE] &&
-                   bW + nW <= a.cap[C_WEIGHT] && (!FM || bIdx + nI <= a.cap[C_FIELD]);
-#else
-  constexpr bool inb = false;
-#endif
   auto put_index = [&](uint64_t r, uint64_t v, uint64_t q) {
     if (imin) note_min(q, v);
-#ifdef FSVM_ABL_NOSTORE  // timing ablation only
-    if (v == 0x123456789ull) a.res[15] = r;
-    return;
-#endif
-    if (inb) {
-      if (a.wide) reinterpret_cast<uint64_t *>(a.index)[r] = v;
-      else reinterpret_cast<uint32_t *>(a.index)[r] = (uint32_t)v;
-      return;
-    }
     if (r < a.cap[C_INDEX]) {
       if (a.wide) out_store(reinterpret_cast<uint64_t *>(a.index) + r, v);
       else out_store(reinterpret_cast<uint32_t *>(a.index) + r, (uint32_t)v);
@@ -2082,10 +1967,6 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
     }
   };
   auto put_value = [&](uint64_t r, float v, uint64_t q) {
-#ifdef FSVM_ABL_NOSTORE
-    if (v == 1234.5f) a.res[15] = r;
-    return;
-#endif
     if (r < a.cap[C_VALUE]) out_store(a.value + r, v);
     else raise_error(a.err, E_CAPACITY, q);
   };
@@ -2099,13 +1980,6 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
   };
   // entry j of the float list of the pass starting at packed counts s
   auto put_float = [&](uint32_t j, float v, uint32_t o, uint64_t s, uint32_t nVp, uint32_t nLp) {
-    if (inb) {  // one store through a selected address
-      float *dst = j < nVp ? a.value + (bVal + fV(s) + j)
-                           : j < nVp + nLp ? a.label + (bRows + fL(s) + (j - nVp))
-                                           : a.weight + (bW + fW(s) + (j - nVp - nLp));
-      *dst = v;
-      return;
-    }
     const uint64_t q = t.tlo + o;
     if (j < nVp) put_value(bVal + fV(s) + j, v, q);
     else if (j < nVp + nLp) put_label(bRows + fL(s) + (j - nVp), v, q);
@@ -2140,7 +2014,7 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
   uint64_t rl = eL;
   for (uint64_t m = so.L; m; m &= m - 1, ++rl) {
     const uint64_t below = (m & (0 - m)) - 1;
-    if (inb || rl < a.cap[C_ROWS]) out_store(a.offset + rl, (uint64_t)(eI + popc64(so.I & below)));
+    if (rl < a.cap[C_ROWS]) out_store(a.offset + rl, (uint64_t)(eI + popc64(so.I & below)));
     else raise_error(a.err, E_CAPACITY, P + ctz64(m));
   }
   if constexpr (!FM) {
@@ -2194,10 +2068,6 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
       if (j < nF0 && !((slowF >> u) & 1u)) put_float(j, fb[u], sh.u.lst[fb0 + j], 0, nV0, nL0);
     }
   }
-#ifndef FSVM_PF_LATE
-  // the next tile's text loads, in flight through the rest of this tile
-  if (PERSIST && kn < a.ntiles) stage_issue(a.text, a.n, (uint64_t)kn * kTile, sr, bk);
-#endif
   for (uint32_t p = 0; p < np; ++p) {
     const uint64_t s = p ? sh.pend[p - 1] : 0, e = p ? sh.pend[p] : pe0;
     if (p) {  // block-uniform
@@ -2209,9 +2079,6 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
     const uint64_t cn = e - s;
     const uint32_t nIp = fI(cn), nVp = fV(cn), nLp = fL(cn), nFp = nVp + nLp + fW(cn), fbp = kIW * nIp;
     const uint32_t u0 = p ? 0u : (uint32_t)kB;
-#ifdef FSVM_UNR2
-#pragma unroll 2
-#endif
     for (uint32_t u = u0, j = (uint32_t)tid + u0 * kFThreads; j < nIp; ++u, j += kFThreads) {
       const uint32_t o = sh.u.lst[j];
       bool ok;
@@ -2219,9 +2086,6 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
       if (ok) put_index(bIdx + fI(s) + j, ids_of(v), t.tlo + o);
       slowI |= (ok ? 0u : 1u) << u;
     }
-#ifdef FSVM_UNR2
-#pragma unroll 2
-#endif
     for (uint32_t u = u0, j = (uint32_t)tid + u0 * kFThreads; j < nFp; ++u, j += kFThreads) {
       const uint32_t o = sh.u.lst[fbp + j];
       bool ok;
@@ -2246,19 +2110,13 @@ DA_HDF uint32_t tile_p(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k, Sta
     if ((tid & (kWave - 1)) == 0 && zm) store_flag_u64(&a.umin[sh.c.c_first - 1], 0);
   }
   FAST_STAMP(k, 8);
-#ifdef FSVM_PF_AHEAD
-  if (pfv == 0xFFu && a.n == 1) a.res[15] = pfv;  // keeps the touch load alive (never true)
-#endif
-#ifdef FSVM_PF_LATE
-  if (PERSIST && kn < a.ntiles) stage_issue(a.text, a.n, (uint64_t)kn * kTile, sr, bk);
-#endif
-  return kn;
 }
 
+// The entry point.  (The body stays one call below it: folded in, the same
+// source compiles to a few scalar instructions in another order.)
 template <int MODE, bool FM = false, class BK>
 DA_HDF void tile(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k) {
-  StageRegs sr;
-  (void)tile_p<MODE, FM, false>(a, sh, bk, k, sr);
+  tile_body<MODE, FM>(a, sh, bk, k);
 }
 
 }  // namespace fsvm

@@ -488,10 +488,6 @@ DA_HDF void tile(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k) {
   const uint32_t cnt4[4] = {nL, nI, nV, nW};  // look-back slots fsvm Q_ROWS, Q_INDEX, Q_VALUE, Q_WEIGHT
   if (tid == 0) publish_aggregate(a.lean_lb, a.ntiles, k, cnt4);
   FAST_STAMP(k, 4);
-#if defined(LSVM_ABL) && LSVM_ABL == 1  // timing ablation only: stage + classify + roles + scan
-  if (ex == 0x123456789ull) a.res[15] = totp;
-  return;
-#endif
   // ---- wave run lists: the wave's first kLCap index runs and value runs in
   // wave rank order, decoded round-robin by the wave's lanes -- every lane
   // decodes about the wave's average, where each lane decoding its own runs
@@ -544,10 +540,6 @@ DA_HDF void tile(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k) {
   }
   bk.wave_sync();
   FAST_STAMP(k, 5);
-#if defined(LSVM_ABL) && LSVM_ABL == 3  // timing ablation only: + run lists
-  if (li[lane] == 0x12345678u) a.res[15] = lv[lane];
-  return;
-#endif
   bool anyfail = false;
   const uint32_t iv = a.indexing_mode > 0 ? 1u : 0u;
   const uint32_t nround = (mx<uint32_t>(nIq, nVq) + kWave - 1) / kWave;  // wave-uniform
@@ -576,10 +568,6 @@ DA_HDF void tile(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k) {
   }
   bk.wave_sync();  // (the failure words and the decoded entries: every lane reads them below)
   FAST_STAMP(k, 6);
-#if defined(LSVM_ABL) && LSVM_ABL == 4  // timing ablation only: + decode, no look-back
-  if (li[lane] == 0x12345678u || anyfail) a.res[15] = lv[lane];
-  return;
-#endif
   // ---- look-back (wave 0), then the stores
   if (tid < kWave) {
     if (!lean_look_back(a.lean_lb, a.ntiles, k, cnt4, a.gate, sh.base, bk) && tid == 0) sh.flags |= 2u;
@@ -602,10 +590,6 @@ DA_HDF void tile(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k) {
   const uint64_t eL = bRows + (ex & 0xFFFF), eW = bW + ((ex >> 16) & 0xFFFF), eI = bIdx + ((ex >> 32) & 0xFFFF),
                  eV = bVal + (ex >> 48);
   const uint64_t eIw = bIdx + ((wpre >> 32) & 0xFFFF), eVw = bVal + (wpre >> 48);  // the wave's first entries
-#if defined(LSVM_ABL) && LSVM_ABL == 2  // timing ablation only: no stores
-  if (eL == 0x123456789ull) a.res[15] = eI + eV + eW;
-  return;
-#endif
   auto put_index = [&](uint64_t r, uint64_t v, uint64_t q) {
     if (r < a.cap[C_INDEX]) {
       if (a.wide) reinterpret_cast<uint64_t *>(a.index)[r] = v;
