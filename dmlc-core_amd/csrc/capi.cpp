@@ -609,6 +609,67 @@ int dmlc_amd_to_csc(const dmlc_amd_csr *csr, const dmlc_amd_result *d_result, co
   return e == hipSuccess ? DMLC_AMD_OK : DMLC_AMD_ERR_HIP;
 }
 
+int dmlc_amd_bins_geometry(uint32_t *cells_per_tile, uint32_t *rows_per_tile) {
+  return dmlc_amd_dense_geometry(cells_per_tile, rows_per_tile);  // the dense tile (bins_core.h)
+}
+
+int dmlc_amd_to_bins(const dmlc_amd_csr *csr, const dmlc_amd_result *d_result, const dmlc_amd_cuts *cuts,
+                     const dmlc_amd_bins_params *prm, void *d_out, uint64_t *d_status, void *stream) {
+  if (!csr || !d_result || !cuts || !prm || !d_out || !d_status) return DMLC_AMD_ERR_ARG;
+  if (!cuts->cut_ptr || (cuts->n_cuts && !cuts->cut_value)) return DMLC_AMD_ERR_ARG;
+  if (prm->index_bits != 32 && prm->index_bits != 64) return DMLC_AMD_ERR_ARG;
+  if (prm->value_type != DMLC_AMD_F32) return DMLC_AMD_ERR_ARG;
+  const int cbytes = prm->code_bytes;
+  if (cbytes != 1 && cbytes != 2 && cbytes != 4) return DMLC_AMD_ERR_ARG;
+  if (cbytes < 4 && (prm->missing_code >> (8 * cbytes)) != 0) return DMLC_AMD_ERR_ARG;
+  if (prm->ncol == 0 || prm->ncol >= (1ull << 32) || prm->ld < prm->ncol) return DMLC_AMD_ERR_ARG;
+  if (prm->flags & ~DMLC_AMD_BINS_GLOBAL) return DMLC_AMD_ERR_ARG;
+  if (prm->reserved[0] || prm->reserved[1] || prm->reserved[2]) return DMLC_AMD_ERR_ARG;
+  if (reinterpret_cast<uintptr_t>(d_out) % (uintptr_t)cbytes) return DMLC_AMD_ERR_ARG;
+  const void *srcs[] = {csr->offset, csr->label,       csr->weight,     csr->qid, csr->field, csr->index,
+                        csr->value,  d_result,         cuts->cut_ptr,   cuts->cut_value};
+  for (const void *s : srcs)
+    if (same_array(d_out, s) || same_array(d_status, s)) return DMLC_AMD_ERR_ARG;
+  // the rows the window can hold, as in dmlc_amd_to_dense
+  const uint64_t cap_rows = csr->cap[DMLC_AMD_ROWS];
+  const uint64_t nrows = prm->row_begin < cap_rows ? dmlc_amd::mn<uint64_t>(prm->max_rows, cap_rows - prm->row_begin) : 0;
+  if (nrows && (!csr->offset || (csr->cap[DMLC_AMD_INDEX] && !csr->index))) return DMLC_AMD_ERR_ARG;
+  dmlc_amd::BinsArgs b;
+  std::memset(&b, 0, sizeof(b));
+  dmlc_amd::DenseArgs &a = b.d;
+  dmlc_amd::dense_shape(prm->ncol, &a.S, &a.R);
+  const uint64_t col_tiles = (prm->ncol - 1) / a.S + 1;
+  const uint64_t row_tiles = nrows ? (nrows - 1) / a.R + 1 : 0;
+  // never truncated: a window of more tiles than the grid holds is refused
+  if (col_tiles > dmlc_amd::kDenseMaxTiles || row_tiles > dmlc_amd::kDenseMaxTiles ||
+      col_tiles * row_tiles > dmlc_amd::kDenseMaxTiles)
+    return DMLC_AMD_ERR_ARG;
+  a.offset = csr->offset;
+  a.index = csr->index;
+  a.value = csr->value;
+  a.res = reinterpret_cast<const uint64_t *>(d_result);
+  a.cap_rows = cap_rows;
+  a.cap_index = csr->cap[DMLC_AMD_INDEX];
+  a.cap_value = csr->value ? csr->cap[DMLC_AMD_VALUE] : 0;
+  a.row_begin = prm->row_begin;
+  a.row_end = prm->row_begin + prm->max_rows < prm->row_begin ? ~0ull : prm->row_begin + prm->max_rows;
+  a.ncol = prm->ncol;
+  a.ld = prm->ld;
+  a.one = 0x3F800000ull;
+  a.col_tiles = (uint32_t)col_tiles;
+  a.out = d_out;
+  a.status = d_status;
+  b.cut_ptr = cuts->cut_ptr;
+  b.cut_value = cuts->cut_value;
+  b.n_cuts = cuts->n_cuts;
+  b.missing = prm->missing_code;
+  b.global_ids = (prm->flags & DMLC_AMD_BINS_GLOBAL) != 0;
+  const hipError_t e = dmlc_amd::launch_bins(b, prm->index_bits == 64, cbytes, (uint32_t)(col_tiles * row_tiles),
+                                             reinterpret_cast<hipStream_t>(stream));
+  g_last_hip = e;
+  return e == hipSuccess ? DMLC_AMD_OK : DMLC_AMD_ERR_HIP;
+}
+
 const char *dmlc_amd_last_hip_error(void) { return hipGetErrorString(g_last_hip); }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 
 #include "args.h"
 #include "dense_core.h"
+#include "bins_core.h"
 #include "gather_core.h"
 #include "csc_core.h"
 
@@ -40,6 +41,9 @@ hipError_t launch_csv(const CsvArgs &a, const FastCsvArgs &f, bool use_fast, uin
 // CSR -> dense row batch (dense_core.h): d_status, then ntiles tiles (0 = d_status only);
 // indices are u32, or u64 when wide; values are 4- or 8-byte bit patterns
 hipError_t launch_dense(const DenseArgs &a, int wide, int value_bytes, uint32_t ntiles, hipStream_t s);
+// CSR -> quantised dense row batch (bins_core.h): d_status, then ntiles tiles (0 = d_status only);
+// indices are u32, or u64 when wide; codes are 1, 2 or 4 bytes
+hipError_t launch_bins(const BinsArgs &b, int wide, int code_bytes, uint32_t ntiles, hipStream_t s);
 // row gather of a CSR (gather_core.h): the tiles' lengths, their scan (d_status, the dst result
 // block), the copy; a.ntiles == 0 runs the scan alone
 hipError_t launch_gather(const GatherArgs &a, int wide, int value_bytes, hipStream_t s);

@@ -47,6 +47,19 @@ class DenseParams(ctypes.Structure):
                 ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
 
 
+class Cuts(ctypes.Structure):
+    """dmlc_amd_cuts (24 bytes)."""
+    _fields_ = [("cut_ptr", ctypes.c_void_p), ("cut_value", ctypes.c_void_p), ("n_cuts", ctypes.c_uint64)]
+
+
+class BinsParams(ctypes.Structure):
+    """dmlc_amd_bins_params (64 bytes)."""
+    _fields_ = [("index_bits", ctypes.c_int32), ("value_type", ctypes.c_int32), ("code_bytes", ctypes.c_int32),
+                ("missing_code", ctypes.c_uint32),
+                ("row_begin", ctypes.c_uint64), ("max_rows", ctypes.c_uint64), ("ncol", ctypes.c_uint64),
+                ("ld", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
 class GatherParams(ctypes.Structure):
     """dmlc_amd_gather_params (32 bytes)."""
     _fields_ = [("index_bits", ctypes.c_int32), ("value_type", ctypes.c_int32), ("label_type", ctypes.c_int32),
@@ -77,6 +90,11 @@ GATHER_FLAG_ERROR, GATHER_FLAG_COUNT, GATHER_FLAG_OFFSET_CAP, GATHER_FLAG_CAPACI
 # d_status words of dmlc_amd_to_dense and its flag bits
 DENSE_ROWS, DENSE_DROPPED, DENSE_FIRST, DENSE_FLAGS = range(4)
 DENSE_FLAG_ERROR, DENSE_FLAG_VALUE_COUNT, DENSE_FLAG_OFFSET_CAP, DENSE_FLAG_ROW_TOO_LONG = 1, 2, 4, 8
+
+# d_status words of dmlc_amd_to_bins (0 - 3 and flag bits 0 - 3 as the dense ones) and its own flag bits
+BINS_ROWS, BINS_DROPPED, BINS_FIRST, BINS_FLAGS, BINS_NAN, BINS_UNBINNED = range(6)
+BINS_FLAG_CODE_RANGE, BINS_FLAG_CUT_PTR = 16, 32
+BINS_GLOBAL = 1
 
 _LIB = None
 
@@ -146,6 +164,13 @@ def lib():
                                           ctypes.c_void_p]
             L.dmlc_amd_csc_geometry.restype = ctypes.c_int
             L.dmlc_amd_csc_geometry.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
+        if hasattr(L, "dmlc_amd_to_bins"):  # (A/B builds of older sources lack it)
+            L.dmlc_amd_to_bins.restype = ctypes.c_int
+            L.dmlc_amd_to_bins.argtypes = [ctypes.POINTER(Csr), ctypes.c_void_p, ctypes.POINTER(Cuts),
+                                           ctypes.POINTER(BinsParams), ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p]
+            L.dmlc_amd_bins_geometry.restype = ctypes.c_int
+            L.dmlc_amd_bins_geometry.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
         L.dmlc_amd_profile_begin.restype = ctypes.c_int
         L.dmlc_amd_profile_end.restype = ctypes.c_int
         L.dmlc_amd_profile_end.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int),
@@ -172,7 +197,8 @@ EXPORTED_SYMBOLS = ("dmlc_amd_parse", "dmlc_amd_workspace_bytes", "dmlc_amd_erro
                     "dmlc_amd_copy", "dmlc_amd_copy_n", "dmlc_amd_copy_n_dev", "dmlc_amd_fast_geometry",
                     "dmlc_amd_build_id", "dmlc_amd_to_dense", "dmlc_amd_dense_geometry", "dmlc_amd_gather_rows",
                     "dmlc_amd_gather_workspace_bytes", "dmlc_amd_gather_geometry", "dmlc_amd_to_csc",
-                    "dmlc_amd_csc_workspace_bytes", "dmlc_amd_csc_geometry")
+                    "dmlc_amd_csc_workspace_bytes", "dmlc_amd_csc_geometry", "dmlc_amd_to_bins",
+                    "dmlc_amd_bins_geometry")
 
 
 def csc_geometry():
@@ -189,6 +215,14 @@ def dense_geometry():
     // S) rows (dmlc_amd_dense_geometry)."""
     c, r = ctypes.c_uint32(0), ctypes.c_uint32(0)
     lib().dmlc_amd_dense_geometry(ctypes.byref(c), ctypes.byref(r))
+    return int(c.value), int(r.value)
+
+
+def bins_geometry():
+    """(cells per tile, most rows per tile) of dmlc_amd_to_bins in the loaded
+    library, read as dense_geometry()'s (dmlc_amd_bins_geometry)."""
+    c, r = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    lib().dmlc_amd_bins_geometry(ctypes.byref(c), ctypes.byref(r))
     return int(c.value), int(r.value)
 
 
@@ -453,6 +487,114 @@ class DeviceParser:
         out["result"] = res
         out["dense"] = dense
         out["dense_status"] = status.cpu().numpy().view(np.uint64)
+        return out
+
+    # ---- quantised dense row batches (dmlc_amd_to_bins)
+    def to_bins_async(self, out, result, bins, cut_ptr, cut_value, *, ncol, row_begin=0, max_rows=None, missing=None,
+                      global_ids=False, status=None, stream=None):
+        """Launch the CSR -> bin codes pass behind whatever fills `result`
+        (same stream, no host sync): rows [row_begin, row_begin + max_rows) of
+        the batch `out` into `bins`, a 2-D device uint8 / int16 / int32 tensor
+        with ncol columns whose dtype chooses the code width (a strided view
+        is fine: ld = bins.stride(0)).  cut_ptr is a device int32 tensor of
+        ncol + 1 words (read as unsigned), cut_value a device float32 tensor:
+        column c's cuts are cut_value[cut_ptr[c] : cut_ptr[c + 1]], ascending.
+        A cell's code is min(#{cuts <= v}, cuts - 1), plus cut_ptr[c] with
+        global_ids; `missing` (default: the all-ones code of that width) goes
+        into cells without an entry, with a NaN or without cuts.  max_rows
+        defaults to bins.shape[0]; rows the parse did not produce stay
+        unwritten.  Returns the device status tensor (int64[8]: rows written,
+        entries dropped, first dropped position, DENSE_FLAG_* | BINS_FLAG_*
+        bits, NaN cells, unbinned cells, 0, 0)."""
+        torch = self.torch
+        if self._value_type() != F32:
+            raise ValueError("to_bins takes float values only")
+        widths = {torch.uint8: 1, torch.int16: 2, torch.int32: 4}
+        if bins.dim() != 2 or int(bins.shape[1]) != int(ncol) or bins.dtype not in widths:
+            raise ValueError("bins must be a 2-D uint8, int16 or int32 tensor with ncol = %d columns" % ncol)
+        if int(ncol) > 1 and bins.stride(1) != 1:
+            raise ValueError("bins rows must be contiguous (stride(1) == 1)")
+        if cut_ptr.dtype != torch.int32 or cut_ptr.dim() != 1 or int(cut_ptr.numel()) < int(ncol) + 1 \
+                or not cut_ptr.is_contiguous():
+            raise ValueError("cut_ptr must be a contiguous int32 tensor of ncol + 1 = %d words" % (int(ncol) + 1))
+        if cut_value.dtype != torch.float32 or cut_value.dim() != 1 or not cut_value.is_contiguous():
+            raise ValueError("cut_value must be a contiguous 1-D float32 tensor")
+        nrow = int(bins.shape[0])
+        if max_rows is None:
+            max_rows = nrow
+        if max_rows > nrow:
+            raise ValueError("max_rows = %d exceeds the %d rows of bins" % (max_rows, nrow))
+        if nrow > 1 and int(bins.stride(0)) < int(ncol):
+            raise ValueError("bins rows overlap (stride(0) = %d < ncol = %d)" % (bins.stride(0), ncol))
+        if status is None:
+            status = torch.empty(8, dtype=torch.int64, device=bins.device)
+        p = BinsParams()
+        p.index_bits = self.params.index_bits
+        p.value_type = F32
+        p.code_bytes = widths[bins.dtype]
+        p.missing_code = (1 << (8 * p.code_bytes)) - 1 if missing is None else int(missing) & 0xFFFFFFFF
+        p.row_begin, p.max_rows, p.ncol = int(row_begin), int(max_rows), int(ncol)
+        p.ld = int(bins.stride(0)) if nrow > 1 else int(ncol)
+        p.flags = BINS_GLOBAL if global_ids else 0
+        c = Cuts()
+        n_cuts = int(cut_value.numel())
+        c.cut_ptr, c.cut_value, c.n_cuts = cut_ptr.data_ptr(), cut_value.data_ptr() if n_cuts else None, n_cuts
+        csr = out.get("_csr") or self.csr_of(out)
+        s = stream if stream is not None else torch.cuda.current_stream()
+        # (an empty tensor has no storage: max_rows == 0 only sets the status, any non-null pointer does)
+        rc = lib().dmlc_amd_to_bins(ctypes.byref(csr), result.data_ptr(), ctypes.byref(c), ctypes.byref(p),
+                                    bins.data_ptr() if nrow else status.data_ptr(), status.data_ptr(),
+                                    s.cuda_stream)
+        if rc != 0:
+            msg = lib().dmlc_amd_error_string(rc).decode()
+            if rc == 33:
+                msg += " (%s)" % lib().dmlc_amd_last_hip_error().decode()
+            raise RuntimeError("dmlc_amd_to_bins: %s" % msg)
+        return status
+
+    def to_bins(self, out, cut_ptr, cut_value, ncol=None, dtype=None, row_begin=0, max_rows=None, missing=None,
+                global_ids=False):
+        """Bin codes of a batch returned by parse() or gather_rows(): (tensor,
+        status) after a sync, status as uint64[8].  dtype (default
+        torch.uint8) chooses the code width.  ncol=None means
+        len(cut_ptr) - 1."""
+        torch = self.torch
+        if ncol is None:
+            ncol = int(cut_ptr.numel()) - 1
+        rows = int(out["counts"][ROWS])
+        if max_rows is None:
+            max_rows = max(rows - int(row_begin), 0)
+        bins = torch.empty((int(max_rows), int(ncol)), dtype=dtype or torch.uint8, device="cuda")
+        status = self.to_bins_async(out, out["result"], bins, cut_ptr, cut_value, ncol=ncol, row_begin=row_begin,
+                                    max_rows=max_rows, missing=missing, global_ids=global_ids)
+        return bins, status.cpu().numpy().view(np.uint64)
+
+    def parse_bins(self, text, chunk_starts, cut_ptr, cut_value, ncol, dtype=None, missing=None, global_ids=False,
+                   stream=None):
+        """Text -> bin codes: count, allocate, then the write pass and the
+        bins pass on one stream with no host sync between the two.  Returns
+        parse()'s dict with "bins" (rows x ncol) and "bins_status"."""
+        torch = self.torch
+        res = torch.zeros(16, dtype=torch.int64, device="cuda")
+        counts = self.count(text, chunk_starts, stream, result=res)
+        out = self.alloc(counts)
+        nchunks = int(chunk_starts.numel()) - 1
+        out["chunk_table"] = torch.zeros(max(nchunks * units_per_chunk(self.params), 1) * 8, dtype=torch.int64,
+                                         device="cuda")
+        bins = torch.empty((int(counts[ROWS]), int(ncol)), dtype=dtype or torch.uint8, device="cuda")
+        self.fill_async(text, chunk_starts, out, res, chunk_table=out["chunk_table"] if nchunks > 0 else None,
+                        stream=stream)
+        status = self.to_bins_async(out, res, bins, cut_ptr, cut_value, ncol=ncol, missing=missing,
+                                    global_ids=global_ids, stream=stream)
+        if stream is not None:
+            stream.synchronize()
+        r = res.cpu().numpy().view(np.uint64)
+        out["error"], out["path"] = int(r[8]), int(r[9])
+        out["result_counts"] = [int(x) for x in r[:8]]
+        out["max_index"], out["max_field"] = int(r[10]), int(r[11])
+        out["result"] = res
+        out["bins"] = bins
+        out["bins_status"] = status.cpu().numpy().view(np.uint64)
         return out
 
     # ---- row gather: shuffle / select rows of a parsed batch (dmlc_amd_gather_rows)

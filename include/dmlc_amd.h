@@ -352,6 +352,85 @@ int dmlc_amd_to_csc(const dmlc_amd_csr *csr, const dmlc_amd_result *d_result, co
  * built with (either pointer may be NULL). */
 int dmlc_amd_csc_geometry(uint32_t *entries_per_tile, uint32_t *radix_bits);
 
+/* Quantised dense row batch from a parsed CSR: what a histogram tree learner
+ * trains on.  The rows [row_begin, row_begin + max_rows) that the parse
+ * produced, as a row-major matrix of ncol columns and leading dimension ld >=
+ * ncol (in elements) at d_out, each element the code_bytes-wide index of the
+ * cell's bin under per-column cut points.  The window and the choice of each
+ * cell's winning entry are dmlc_amd_to_dense's.  With rows =
+ * min(result.count[ROWS], csr.cap[ROWS]):
+ *
+ *   for r in row_begin .. min(rows, row_begin + max_rows) - 1:
+ *     win[0 .. ncol-1] = none
+ *     for k in offset[r] .. offset[r+1]-1, ascending:
+ *       c = index[k]                            (compared as 64-bit)
+ *       if c < ncol: win[c] = count[VALUE] == 0 ? 1.0f : value[k]     (the last wins)
+ *       else:        dropped += 1; first_dropped = min(first_dropped, k)
+ *     for c in 0 .. ncol-1:
+ *       code = missing_code
+ *       if win[c] != none:
+ *         v = win[c]; b = cut_ptr[c]; e = cut_ptr[c+1]; m = e - b
+ *         if b > e or e > n_cuts: unbinned += 1; flags |= CUT_PTR
+ *         else if m == 0:         unbinned += 1
+ *         else if v is NaN:       nan += 1
+ *         else:
+ *           x = min(#{i in [b, e) : cut_value[i] <= v}, m - 1)       (IEEE compare)
+ *           if flags & DMLC_AMD_BINS_GLOBAL: x += b
+ *           if x fits code_bytes and x != missing_code: code = x
+ *           else: flags |= CODE_RANGE
+ *       out[(r - row_begin) * ld + c] = code
+ *
+ * x is the upper bound clamped to the last bin (XGBoost's
+ * HistogramCuts::SearchBin; numpy's searchsorted(side="right") clipped to m -
+ * 1): -0.0 == 0.0, -inf gives 0 and +inf gives m - 1.  cut_value is ascending
+ * inside a column and holds no NaN; otherwise that column's codes are
+ * unspecified (and still no access leaves the capacities).  No element of
+ * cut_value at or past n_cuts is read.  Elements between ncol and ld, and rows
+ * of d_out past the parsed row count, are never written; d_out is never read.
+ * libfm's field array is ignored. */
+typedef struct dmlc_amd_cuts { /* device arrays */
+  const uint32_t *cut_ptr;     /* ncol + 1 words: column c owns cut_value[cut_ptr[c] .. cut_ptr[c+1]) */
+  const float *cut_value;      /* n_cuts floats (may be NULL when n_cuts == 0) */
+  uint64_t n_cuts;             /* capacity of cut_value: bounds every read */
+} dmlc_amd_cuts;
+
+#define DMLC_AMD_BINS_GLOBAL 1u /* codes are positions in cut_value: cut_ptr[c] is added */
+typedef struct dmlc_amd_bins_params {
+  int32_t index_bits;    /* 32 | 64 */
+  int32_t value_type;    /* DMLC_AMD_F32 only */
+  int32_t code_bytes;    /* 1 | 2 | 4: width of an output element */
+  uint32_t missing_code; /* must fit code_bytes */
+  uint64_t row_begin, max_rows, ncol, ld; /* as dmlc_amd_dense_params; ld in elements */
+  uint32_t flags, reserved[3];            /* flags: DMLC_AMD_BINS_GLOBAL | 0 */
+} dmlc_amd_bins_params;
+
+/* d_status: uint64_t[8] in device memory, set by the call itself.  Words 0 - 3
+ * are DMLC_AMD_DENSE_ROWS / DROPPED / FIRST / FLAGS with the dense flag bits 0 -
+ * 3 (with bits 0 or 1 nothing is written to d_out); words 6 and 7 are 0. */
+enum {
+  DMLC_AMD_BINS_NAN = 4,     /* cells whose winning value was NaN */
+  DMLC_AMD_BINS_UNBINNED = 5 /* cells with an entry in a column with no usable cuts */
+};
+#define DMLC_AMD_BINS_FLAG_CODE_RANGE 16u /* a code did not fit code_bytes or equalled missing_code: stored as
+                                             missing_code */
+#define DMLC_AMD_BINS_FLAG_CUT_PTR 32u    /* a cell's column has cut_ptr[c] > cut_ptr[c+1] or cut_ptr[c+1] > n_cuts */
+
+/* Asynchronous on `stream`, after whatever fills *d_result; no host
+ * synchronisation, allocation or device-wide barrier, and no workgroup waits
+ * for another.  Returns DMLC_AMD_ERR_ARG before any HIP call for a null
+ * pointer, ncol == 0 or ncol >= 2^32, ld < ncol, bad index_bits / value_type
+ * (integer values are not binned) / code_bytes, a missing_code that does not
+ * fit code_bytes, an unknown flag or a non-zero reserved word, d_out not
+ * aligned to its element, d_out or d_status being one of the source's arrays,
+ * its result block or a cut array, or a window of more tiles than one launch
+ * holds (2^31 - 1; see dmlc_amd_bins_geometry).  max_rows == 0 only sets
+ * d_status. */
+int dmlc_amd_to_bins(const dmlc_amd_csr *csr, const dmlc_amd_result *d_result, const dmlc_amd_cuts *cuts,
+                     const dmlc_amd_bins_params *prm, void *d_out, uint64_t *d_status /* [8] */, void *stream);
+
+/* Tile geometry, as dmlc_amd_dense_geometry (either pointer may be NULL). */
+int dmlc_amd_bins_geometry(uint32_t *cells_per_tile, uint32_t *rows_per_tile);
+
 /* Batch dmlc::strtof (ParseFloat<float>, strtonum.h:95-264, :279-281): string i
  * is d_text[d_offsets[i] .. d_offsets[i+1]) read as NUL-terminated at its end.
  * Writes the value, the bytes consumed (endptr - nptr) and the "Invalid NAN
