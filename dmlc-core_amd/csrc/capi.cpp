@@ -670,6 +670,122 @@ int dmlc_amd_to_bins(const dmlc_amd_csr *csr, const dmlc_amd_result *d_result, c
   return e == hipSuccess ? DMLC_AMD_OK : DMLC_AMD_ERR_HIP;
 }
 
+int dmlc_amd_make_cuts_geometry(uint32_t *entries_per_tile, uint32_t *radix_bits) {
+  if (entries_per_tile) *entries_per_tile = dmlc_amd::kCutsTile;
+  if (radix_bits) *radix_bits = dmlc_amd::kCutsRadixBits;
+  return DMLC_AMD_OK;
+}
+
+namespace {
+// the workspace of a make_cuts call (cuts_core.h), every part in whole 256-byte
+// lines: meta, the digit totals, the tile records, the histogram, the two
+// (column, key) buffers, and each column's first sorted entry and sample count
+struct CutsLayout {
+  uint64_t ntiles, passes;
+  uint64_t total, rec, hist, col[2], key[2], cstart, cn;  // byte offsets
+  uint64_t bytes;
+};
+bool cuts_prm_ok(const dmlc_amd_make_cuts_params *prm) {
+  if (!prm) return false;
+  if (prm->index_bits != 32 && prm->index_bits != 64) return false;
+  if (prm->value_type != DMLC_AMD_F32) return false;
+  if (prm->ncol == 0 || prm->max_bin == 0) return false;
+  if (prm->ncol >= (1ull << 32) || prm->ncol * (uint64_t)prm->max_bin >= (1ull << 32)) return false;
+  if (prm->flags || prm->reserved[0] || prm->reserved[1]) return false;
+  return true;
+}
+CutsLayout cuts_layout(uint64_t m, uint64_t ncol) {
+  CutsLayout L;
+  std::memset(&L, 0, sizeof(L));
+  auto up = [](uint64_t b) { return (b + 255) & ~255ull; };
+  L.ntiles = m / dmlc_amd::kCutsTile + (m % dmlc_amd::kCutsTile != 0);
+  if (L.ntiles == 0) L.ntiles = 1;
+  L.passes = dmlc_amd::kCutsKeyPasses + dmlc_amd::cuts_col_passes(ncol);
+  uint64_t at = 256;  // meta
+  L.total = at;
+  at += up(dmlc_amd::kCutsDigits * 4);
+  L.rec = at;
+  at += up(L.ntiles * dmlc_amd::kCutsRecWords * 8);
+  L.hist = at;
+  at += up(L.ntiles * dmlc_amd::kCutsDigits * 4);
+  for (int b = 0; b < 2; ++b) {
+    L.col[b] = at;
+    at += up(m * 4);
+    L.key[b] = at;
+    at += up(m * 4);
+  }
+  L.cstart = at;
+  at += up((ncol + 1) * 4);
+  L.cn = at;
+  at += up(ncol * 4);
+  L.bytes = at;
+  return L;
+}
+}  // namespace
+
+size_t dmlc_amd_make_cuts_workspace_bytes(uint64_t max_entries, uint64_t ncol, const dmlc_amd_make_cuts_params *prm) {
+  if (!cuts_prm_ok(prm) || ncol == 0 || ncol * (uint64_t)prm->max_bin >= (1ull << 32) || ncol >= (1ull << 32) ||
+      max_entries >= dmlc_amd::kCutsMaxWindow)
+    return 0;
+  return (size_t)cuts_layout(max_entries, ncol).bytes;
+}
+
+int dmlc_amd_make_cuts(const dmlc_amd_csr *csr, const dmlc_amd_result *d_result, const dmlc_amd_make_cuts_params *prm,
+                       const dmlc_amd_cuts_out *out, uint64_t *d_status, void *d_workspace, size_t workspace_bytes,
+                       void *stream) {
+  if (!csr || !d_result || !prm || !out || !d_status || !d_workspace) return DMLC_AMD_ERR_ARG;
+  if (!out->cut_ptr || (out->cap && !out->cut_value)) return DMLC_AMD_ERR_ARG;
+  if (!cuts_prm_ok(prm)) return DMLC_AMD_ERR_ARG;
+  // the rows and entries the window can hold: the parsed counts are known on
+  // the device only, so tiles are launched for the bound and leave early past them
+  const uint64_t cap_rows = csr->offset ? csr->cap[DMLC_AMD_ROWS] : 0;
+  const uint64_t cap_index = csr->index ? csr->cap[DMLC_AMD_INDEX] : 0;
+  const uint64_t nrows = prm->row_begin < cap_rows ? dmlc_amd::mn<uint64_t>(prm->max_rows, cap_rows - prm->row_begin) : 0;
+  const uint64_t m = prm->max_entries ? dmlc_amd::mn<uint64_t>(prm->max_entries, cap_index) : cap_index;
+  if (nrows >= dmlc_amd::kCutsMaxWindow || m >= dmlc_amd::kCutsMaxWindow) return DMLC_AMD_ERR_ARG;
+  const CutsLayout L = cuts_layout(m, prm->ncol);
+  if (workspace_bytes < L.bytes) return DMLC_AMD_ERR_ARG;
+  const void *srcs[] = {csr->offset, csr->label, csr->weight, csr->qid, csr->field, csr->index, csr->value, d_result};
+  const void *outs[] = {out->cut_ptr, out->cut_value, d_status, d_workspace};
+  for (const void *o : outs)
+    for (const void *s : srcs)
+      if (same_array(o, s)) return DMLC_AMD_ERR_ARG;
+  dmlc_amd::MakeCutsArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.offset = csr->offset;
+  a.index = csr->index;
+  a.value = reinterpret_cast<const uint32_t *>(csr->value);
+  a.res = reinterpret_cast<const uint64_t *>(d_result);
+  a.cap_rows = cap_rows;
+  a.cap_index = cap_index;
+  a.cap_value = csr->value ? csr->cap[DMLC_AMD_VALUE] : 0;
+  a.row_begin = prm->row_begin;
+  a.row_end = prm->row_begin + prm->max_rows < prm->row_begin ? ~0ull : prm->row_begin + prm->max_rows;
+  a.ncol = prm->ncol;
+  a.max_entries = m;
+  a.ntiles = L.ntiles;
+  a.max_bin = prm->max_bin;
+  a.passes = (uint32_t)L.passes;
+  a.cut_ptr = out->cut_ptr;
+  a.cut_value = reinterpret_cast<uint32_t *>(out->cut_value);
+  a.cap = out->cap;
+  a.status = d_status;
+  char *ws = static_cast<char *>(d_workspace);
+  a.meta = reinterpret_cast<uint64_t *>(ws);
+  a.total = reinterpret_cast<uint32_t *>(ws + L.total);
+  a.rec = reinterpret_cast<uint64_t *>(ws + L.rec);
+  a.hist = reinterpret_cast<uint32_t *>(ws + L.hist);
+  for (int b = 0; b < 2; ++b) {
+    a.col[b] = reinterpret_cast<uint32_t *>(ws + L.col[b]);
+    a.key[b] = reinterpret_cast<uint32_t *>(ws + L.key[b]);
+  }
+  a.cstart = reinterpret_cast<uint32_t *>(ws + L.cstart);
+  a.cn = reinterpret_cast<uint32_t *>(ws + L.cn);
+  const hipError_t e = dmlc_amd::launch_make_cuts(a, prm->index_bits == 64, reinterpret_cast<hipStream_t>(stream));
+  g_last_hip = e;
+  return e == hipSuccess ? DMLC_AMD_OK : DMLC_AMD_ERR_HIP;
+}
+
 const char *dmlc_amd_last_hip_error(void) { return hipGetErrorString(g_last_hip); }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 #include "bins_core.h"
 #include "gather_core.h"
 #include "csc_core.h"
+#include "cuts_core.h"
 
 namespace dmlc_amd {
 
@@ -50,5 +51,9 @@ hipError_t launch_gather(const GatherArgs &a, int wide, int value_bytes, hipStre
 // CSC transpose of a CSR's row window (csc_core.h): hist, scan, scatter per digit pass (a.passes,
 // a.ntiles >= 1 tiles each), then col_offset from the sorted columns when there are several passes
 hipError_t launch_csc(const CscArgs &a, int wide, int value_bytes, hipStream_t s);
+// per-column quantile cuts of a CSR's row window (cuts_core.h): hist, scan, scatter per digit pass
+// (a.passes = four over the key + the column's, a.ntiles >= 1 tiles each), then bounds, count, ptr, write
+using MakeCutsArgs = CutsArgs;
+hipError_t launch_make_cuts(const MakeCutsArgs &a, int wide, hipStream_t s);
 
 }  // namespace dmlc_amd

@@ -79,6 +79,22 @@ class Csc(ctypes.Structure):
                 ("pos", ctypes.c_void_p), ("cap", ctypes.c_uint64)]
 
 
+class CutsOut(ctypes.Structure):
+    """dmlc_amd_cuts_out (24 bytes): dmlc_amd_cuts's layout, cap in n_cuts's place."""
+    _fields_ = [("cut_ptr", ctypes.c_void_p), ("cut_value", ctypes.c_void_p), ("cap", ctypes.c_uint64)]
+
+
+class MakeCutsParams(ctypes.Structure):
+    """dmlc_amd_make_cuts_params (56 bytes)."""
+    _fields_ = [("index_bits", ctypes.c_int32), ("value_type", ctypes.c_int32),
+                ("row_begin", ctypes.c_uint64), ("max_rows", ctypes.c_uint64), ("ncol", ctypes.c_uint64),
+                ("max_entries", ctypes.c_uint64), ("max_bin", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 2)]
+
+
+# d_status words 4 - 6 of dmlc_amd_make_cuts (0 - 3 and the flag bits are to_csc's)
+CUTS_NAN, CUTS_N_CUTS, CUTS_EMPTY_COLS = 4, 5, 6
+
 # d_status words of dmlc_amd_to_csc and its flag bits
 CSC_KEPT, CSC_DROPPED, CSC_FIRST, CSC_FLAGS = range(4)
 CSC_FLAG_ERROR, CSC_FLAG_VALUE_COUNT, CSC_FLAG_OFFSET_CAP, CSC_FLAG_CAPACITY, CSC_FLAG_MAX_ENTRIES = 1, 2, 4, 8, 16
@@ -171,6 +187,16 @@ def lib():
                                            ctypes.c_void_p]
             L.dmlc_amd_bins_geometry.restype = ctypes.c_int
             L.dmlc_amd_bins_geometry.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
+        if hasattr(L, "dmlc_amd_make_cuts"):  # (A/B builds of older sources lack it)
+            L.dmlc_amd_make_cuts_workspace_bytes.restype = ctypes.c_size_t
+            L.dmlc_amd_make_cuts_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64,
+                                                             ctypes.POINTER(MakeCutsParams)]
+            L.dmlc_amd_make_cuts.restype = ctypes.c_int
+            L.dmlc_amd_make_cuts.argtypes = [ctypes.POINTER(Csr), ctypes.c_void_p, ctypes.POINTER(MakeCutsParams),
+                                             ctypes.POINTER(CutsOut), ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_size_t, ctypes.c_void_p]
+            L.dmlc_amd_make_cuts_geometry.restype = ctypes.c_int
+            L.dmlc_amd_make_cuts_geometry.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
         L.dmlc_amd_profile_begin.restype = ctypes.c_int
         L.dmlc_amd_profile_end.restype = ctypes.c_int
         L.dmlc_amd_profile_end.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int),
@@ -198,7 +224,8 @@ EXPORTED_SYMBOLS = ("dmlc_amd_parse", "dmlc_amd_workspace_bytes", "dmlc_amd_erro
                     "dmlc_amd_build_id", "dmlc_amd_to_dense", "dmlc_amd_dense_geometry", "dmlc_amd_gather_rows",
                     "dmlc_amd_gather_workspace_bytes", "dmlc_amd_gather_geometry", "dmlc_amd_to_csc",
                     "dmlc_amd_csc_workspace_bytes", "dmlc_amd_csc_geometry", "dmlc_amd_to_bins",
-                    "dmlc_amd_bins_geometry")
+                    "dmlc_amd_bins_geometry", "dmlc_amd_make_cuts", "dmlc_amd_make_cuts_workspace_bytes",
+                    "dmlc_amd_make_cuts_geometry")
 
 
 def csc_geometry():
@@ -206,6 +233,14 @@ def csc_geometry():
     library (dmlc_amd_csc_geometry)."""
     t, b = ctypes.c_uint32(0), ctypes.c_uint32(0)
     lib().dmlc_amd_csc_geometry(ctypes.byref(t), ctypes.byref(b))
+    return int(t.value), int(b.value)
+
+
+def make_cuts_geometry():
+    """(entries per tile, bits per digit pass) of dmlc_amd_make_cuts in the
+    loaded library (dmlc_amd_make_cuts_geometry)."""
+    t, b = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    lib().dmlc_amd_make_cuts_geometry(ctypes.byref(t), ctypes.byref(b))
     return int(t.value), int(b.value)
 
 
@@ -297,6 +332,7 @@ class DeviceParser:
         self._ws = None
         self._gws = None  # gather_rows_async's workspace
         self._cws = None  # to_csc_async's
+        self._qws = None  # make_cuts_async's
 
     def _workspace(self, nbytes, nchunks):
         need = lib().dmlc_amd_workspace_bytes(nbytes, nchunks, ctypes.byref(self.params))
@@ -596,6 +632,81 @@ class DeviceParser:
         out["bins"] = bins
         out["bins_status"] = status.cpu().numpy().view(np.uint64)
         return out
+
+    # ---- per-column quantile cut points (dmlc_amd_make_cuts)
+    def make_cuts_async(self, out, result, cut_ptr, cut_value, status=None, *, ncol, max_bin=256, row_begin=0,
+                        max_rows=None, stream=None):
+        """Launch the quantile sketch behind whatever fills `result` (same
+        stream, no host sync): for every column below ncol the deduplicated
+        exact rank quantiles (at most max_bin cuts, the last just above the
+        column's maximum) of the entries in rows [row_begin, row_begin +
+        max_rows) of the batch `out`.  cut_ptr is a device int32 tensor of
+        ncol + 1 words (written as unsigned), cut_value a device float32
+        tensor whose length is the capacity (ncol * max_bin always suffices);
+        both go straight into to_bins_async.  Returns the device status tensor
+        (int64[8]: entries kept, entries dropped, first dropped position,
+        CSC_FLAG_* bits, NaN samples, cuts, columns without cuts, 0)."""
+        torch = self.torch
+        if self._value_type() != F32:
+            raise ValueError("make_cuts takes float values only")
+        if cut_ptr.dtype != torch.int32 or cut_ptr.dim() != 1 or int(cut_ptr.numel()) < int(ncol) + 1 \
+                or not cut_ptr.is_contiguous():
+            raise ValueError("cut_ptr must be a contiguous int32 tensor of ncol + 1 = %d words" % (int(ncol) + 1))
+        if cut_value.dtype != torch.float32 or cut_value.dim() != 1 or not cut_value.is_contiguous():
+            raise ValueError("cut_value must be a contiguous 1-D float32 tensor")
+        if status is None:
+            status = torch.empty(8, dtype=torch.int64, device=cut_ptr.device)
+        p = MakeCutsParams()
+        p.index_bits = self.params.index_bits
+        p.value_type = F32
+        p.row_begin = int(row_begin)
+        p.max_rows = (1 << 64) - 1 if max_rows is None else int(max_rows)
+        p.ncol = int(ncol)
+        p.max_bin = int(max_bin)
+        src = out.get("_csr") or self.csr_of(out)
+        m = int(src.cap[INDEX])
+        p.max_entries = m
+        need = lib().dmlc_amd_make_cuts_workspace_bytes(m, int(ncol), ctypes.byref(p))
+        if need == 0:
+            raise ValueError("dmlc_amd_make_cuts: bad ncol = %d or max_bin = %d (ncol * max_bin < 2^32), or a batch "
+                             "of 2^32 - 1 or more entries" % (int(ncol), int(max_bin)))
+        if self._qws is None or self._qws.numel() < need:
+            self._qws = torch.empty(need, dtype=torch.uint8, device="cuda")
+        c = CutsOut()
+        cap = int(cut_value.numel())
+        c.cut_ptr, c.cut_value, c.cap = cut_ptr.data_ptr(), cut_value.data_ptr() if cap else None, cap
+        s = stream if stream is not None else torch.cuda.current_stream()
+        rc = lib().dmlc_amd_make_cuts(ctypes.byref(src), result.data_ptr(), ctypes.byref(p), ctypes.byref(c),
+                                      status.data_ptr(), self._qws.data_ptr(), self._qws.numel(), s.cuda_stream)
+        if rc != 0:
+            msg = lib().dmlc_amd_error_string(rc).decode()
+            if rc == 33:
+                msg += " (%s)" % lib().dmlc_amd_last_hip_error().decode()
+            raise RuntimeError("dmlc_amd_make_cuts: %s" % msg)
+        return status
+
+    def make_cuts(self, out, ncol=None, max_bin=256, row_begin=0, max_rows=None):
+        """Cut points of a batch returned by parse() or gather_rows():
+        (cut_ptr int32[ncol + 1], cut_value float32[N_CUTS], status uint64[8])
+        after a sync.  ncol=None means max_index + 1, which needs a parser made
+        with flags=FLAG_MAX_INDEX.  Raises on a failed parse, a bad value
+        count, a capacity overflow or a truncated window (flag bits 0, 1, 3,
+        4)."""
+        torch = self.torch
+        if ncol is None:
+            if not self.params.flags & FLAG_MAX_INDEX:
+                raise ValueError("ncol=None needs a parse made with FLAG_MAX_INDEX (result.max_index)")
+            ncol = int(out["max_index"]) + 1
+        # a column holds at most min(max_bin, its samples) cuts
+        cap = min(int(ncol) * int(max_bin), int(out["counts"][INDEX]))
+        cut_ptr = torch.empty(int(ncol) + 1, dtype=torch.int32, device="cuda")
+        cut_value = torch.empty(cap, dtype=torch.float32, device="cuda")
+        status = self.make_cuts_async(out, out["result"], cut_ptr, cut_value, ncol=ncol, max_bin=max_bin,
+                                      row_begin=row_begin, max_rows=max_rows).cpu().numpy().view(np.uint64)
+        bad = int(status[CSC_FLAGS]) & (CSC_FLAG_ERROR | CSC_FLAG_VALUE_COUNT | CSC_FLAG_CAPACITY | CSC_FLAG_MAX_ENTRIES)
+        if bad:
+            raise RuntimeError("dmlc_amd_make_cuts: status flags %#x" % int(status[CSC_FLAGS]))
+        return cut_ptr, cut_value[:int(status[CUTS_N_CUTS])], status
 
     # ---- row gather: shuffle / select rows of a parsed batch (dmlc_amd_gather_rows)
     def gather_rows_async(self, out, result, ids, dst=None, dst_result=None, status=None, stream=None):

@@ -431,6 +431,97 @@ int dmlc_amd_to_bins(const dmlc_amd_csr *csr, const dmlc_amd_result *d_result, c
 /* Tile geometry, as dmlc_amd_dense_geometry (either pointer may be NULL). */
 int dmlc_amd_bins_geometry(uint32_t *cells_per_tile, uint32_t *rows_per_tile);
 
+/* Per-column quantile cut points from a parsed CSR: the cuts dmlc_amd_to_bins
+ * quantises under, so parse -> (gather_rows) -> make_cuts -> to_bins runs on
+ * one stream with no host round trip.  Exact rank quantiles over the entries
+ * present in rows [row_begin, row_begin + max_rows), deduplicated (a column with
+ * few distinct values gets few cuts); a column's last cut lies just above its
+ * maximum.  `csr` and *d_result are a parse's or a gather's, unchanged.  The row
+ * window, the clamping of offsets to the index / value capacity and the dropped
+ * entries are dmlc_amd_to_csc's: an entry is dropped when index >= ncol
+ * (compared as 64-bit).  Every other entry of the window is a sample of its
+ * column, duplicates of one cell each counted; without a value array
+ * (count[VALUE] == 0) every sample is 1.0f.
+ *
+ * All ordering is on an unsigned 32-bit key of the float's bits b; there is no
+ * float compare and no float arithmetic, so the results are bit-exact:
+ *
+ *   if b == 0x80000000: b = 0                            (-0.0 counts as +0.0)
+ *   if (b & 0x7fffffff) > 0x7f800000: key = 0xffffffff   (any NaN: sorts last, is no sample)
+ *   else key = (b >> 31) ? ~b : b | 0x80000000
+ *   unkey(k) = (k >> 31) ? k & 0x7fffffff : ~k
+ *
+ *   n_cuts = nan = empty = 0
+ *   for c in 0 .. ncol-1:
+ *     cut_ptr[c] = n_cuts
+ *     s[0 .. n) = the ascending keys of column c's non-NaN samples; nan += its NaN samples
+ *     if n == 0: empty += 1; continue       (to_bins counts the column's cells as UNBINNED)
+ *     B = max_bin;  t[i] = s[floor(i * n / B)] for i in 0 .. B-1        (64-bit product)
+ *     for i in 1 .. B-1: if t[i] > t[i-1]: emit unkey(t[i])             (every cut is > the minimum)
+ *     top = s[n-1];  last = top == 0xff800000 (+inf) ? top : top + 1
+ *     emit unkey(last), bits 0x80000000 stored as 0x00000000
+ *   cut_ptr[ncol] = n_cuts
+ *   (emit v: if n_cuts < out.cap: cut_value[n_cuts] = v;  n_cuts += 1)
+ *
+ * Under to_bins's code min(#{cuts <= v}, m - 1), N distinct values with max_bin
+ * dividing N fall N / max_bin to a bin.  All ncol + 1 words of cut_ptr are
+ * written whatever the input; an empty window gives all zeros.  With n_cuts >
+ * out.cap no element of cut_value at or past cap is written, cut_ptr and the
+ * status stay exact and flag bit 3 is set.  The outputs are a dmlc_amd_cuts
+ * {cut_ptr, cut_value, n_cuts = out.cap} for dmlc_amd_to_bins, which never
+ * reads past what cut_ptr names.  Two runs give the same bytes. */
+typedef struct dmlc_amd_cuts_out {
+  uint32_t *cut_ptr; /* ncol + 1 words */
+  float *cut_value;  /* cap floats (may be NULL when cap == 0) */
+  uint64_t cap;
+} dmlc_amd_cuts_out;
+
+typedef struct dmlc_amd_make_cuts_params {
+  int32_t index_bits; /* 32 | 64 */
+  int32_t value_type; /* DMLC_AMD_F32 only */
+  uint64_t row_begin, max_rows, ncol, max_entries; /* as dmlc_amd_csc_params; max_entries 0 = csr.cap[INDEX] */
+  uint32_t max_bin;            /* >= 1; ncol * max_bin < 2^32 */
+  uint32_t flags, reserved[2]; /* 0 */
+} dmlc_amd_make_cuts_params;
+
+/* d_status: uint64_t[8] in device memory, set by the call itself.  Words 0 - 3
+ * are DMLC_AMD_CSC_KEPT / DROPPED / FIRST / FLAGS (KEPT includes the NaN
+ * samples); the flag bits are DMLC_AMD_CSC_FLAG_*: with ERROR or VALUE_COUNT
+ * cut_ptr is all 0, N_CUTS is 0 and cut_value is untouched; CAPACITY means
+ * N_CUTS > out.cap; MAX_ENTRIES that only the window's first max_entries
+ * entries were sampled.  Word 7 is 0. */
+enum {
+  DMLC_AMD_CUTS_NAN = 4,       /* samples left out as NaN */
+  DMLC_AMD_CUTS_N_CUTS = 5,    /* == cut_ptr[ncol] (exact, also past out.cap) */
+  DMLC_AMD_CUTS_EMPTY_COLS = 6 /* columns with no cut */
+};
+
+/* Bytes of device workspace a call with this bound on the window's entries
+ * (not 0 here: pass csr.cap[INDEX] for the default) and these parameters
+ * needs; 0 for parameters the call would refuse. */
+size_t dmlc_amd_make_cuts_workspace_bytes(uint64_t max_entries, uint64_t ncol, const dmlc_amd_make_cuts_params *prm);
+
+/* Asynchronous on `stream`, after whatever fills *d_result: a fixed sequence of
+ * plain launches sized by max_entries and ncol (three per 8-bit digit of the
+ * key and of ncol - 1, then four more; see dmlc_amd_make_cuts_geometry), no
+ * host synchronisation, allocation or device-wide barrier, and no workgroup
+ * waits for another.  The capacities bound every read and write.  Returns
+ * DMLC_AMD_ERR_ARG before any HIP call for a null pointer (out.cut_value may be
+ * NULL when out.cap == 0), ncol == 0, max_bin == 0, ncol * max_bin >= 2^32
+ * (which keeps cut_ptr at 32 bits), bad index_bits, a value_type other than
+ * F32, a non-zero reserved word or an unknown flag, a workspace that is too
+ * small, an output, the status or the workspace being one of the source's
+ * arrays or its result block, or a window that can hold 2^32 - 1 or more rows
+ * or entries (min(max_rows, cap[ROWS] - row_begin) rows, max_entries entries:
+ * split the rows over several calls). */
+int dmlc_amd_make_cuts(const dmlc_amd_csr *csr, const dmlc_amd_result *d_result, const dmlc_amd_make_cuts_params *prm,
+                       const dmlc_amd_cuts_out *out, uint64_t *d_status /* [8] */, void *d_workspace,
+                       size_t workspace_bytes, void *stream);
+
+/* Entries per tile (one workgroup) and bits per digit pass this library was
+ * built with (either pointer may be NULL). */
+int dmlc_amd_make_cuts_geometry(uint32_t *entries_per_tile, uint32_t *radix_bits);
+
 /* Batch dmlc::strtof (ParseFloat<float>, strtonum.h:95-264, :279-281): string i
  * is d_text[d_offsets[i] .. d_offsets[i+1]) read as NUL-terminated at its end.
  * Writes the value, the bytes consumed (endptr - nptr) and the "Invalid NAN
