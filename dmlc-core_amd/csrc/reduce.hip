@@ -33,13 +33,20 @@ __global__ void __launch_bounds__(256) max_kernel(const T *a, const uint64_t *co
   }
 }
 
+// The result word is reset by a launch of its own and not by hipMemsetAsync, so
+// that a captured call holds kernel nodes only: the memset nodes of a captured
+// parse -> gather -> ... graph wrote other bytes than 0 from its second replay
+// on (tests/test_gpu_graph.py).
+__global__ void max_reset_kernel(unsigned long long *out) { *out = 0; }
+
 }  // namespace
 
 hipError_t launch_max(const void *arr, int wide, const uint64_t *count, uint64_t cap, uint64_t *out,
                       hipStream_t s) {
-  hipError_t e = hipMemsetAsync(out, 0, sizeof(uint64_t), s);
-  if (e != hipSuccess || !arr || cap == 0) return e;
   unsigned long long *o = reinterpret_cast<unsigned long long *>(out);
+  max_reset_kernel<<<1, 1, 0, s>>>(o);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || !arr || cap == 0) return e;
   if (wide) max_kernel<uint64_t><<<1024, 256, 0, s>>>(static_cast<const uint64_t *>(arr), count, cap, o);
   else max_kernel<uint32_t><<<1024, 256, 0, s>>>(static_cast<const uint32_t *>(arr), count, cap, o);
   return hipGetLastError();

@@ -324,7 +324,13 @@ class DeviceParser:
     """One parser configuration bound to the current HIP device.
 
     parse(text, chunk_starts) takes a device uint8 tensor and a device int64
-    tensor of nchunks+1 chunk boundaries and returns device tensors."""
+    tensor of nchunks+1 chunk boundaries and returns device tensors.
+
+    The *_into / *_async calls with every buffer passed in can be captured into
+    a graph (torch.cuda.graph) once an eager call has grown the workspaces: a
+    workspace that has to grow is freed and allocated anew, and a graph
+    captured earlier would keep the freed pointer.  So capture the largest
+    input first, or use one parser per graph."""
 
     def __init__(self, fmt="libsvm", **kw):
         self.params = make_params(fmt, **kw)
