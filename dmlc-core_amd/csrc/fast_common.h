@@ -251,6 +251,57 @@ DA_HD Nib classify_dword_lut(uint32_t x, const uint32_t *cls) {
   return r;
 }
 
+// One 16-byte unit (w, as staged) through the table: its four 16-bit plane
+// pieces, bit b <-> byte b of the unit, as classify64_lut's planes have them.
+struct Piece16 {
+  uint32_t dg, nc;  // D | G << 16, N | C << 16
+};
+DA_HD Piece16 classify16_lut(const uint32_t w[4], const uint32_t *cls) {
+  uint32_t acc[2];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int i = 4 * j + b;
+      const uint32_t x = cls[cls_index((w[j] >> (8 * b)) & 0xFFu)];
+      if ((i & 7) == 0) acc[i >> 3] = x;
+      else acc[i >> 3] |= x << (i & 7);
+    }
+  // byte p of acc[h] = plane p of bytes 8h..8h+7
+  Piece16 r;
+  r.dg = perm_b32(acc[1], acc[0], 0x05010400u);
+  r.nc = perm_b32(acc[1], acc[0], 0x07030602u);
+  return r;
+}
+
+// The value of the lane d (1 or 2) away inside the caller's quad of lanes
+// (lane ^ d; all four lanes active): a DPP quad_perm move on the device.
+template <int D, class BK>
+DA_HDF uint32_t quad_swap(uint32_t v, BK &bk) {
+  static_assert(D == 1 || D == 2, "a neighbour inside the quad");
+#if defined(__HIP_DEVICE_COMPILE__)
+  (void)bk;  // quad_perm:[1,0,3,2] / [2,3,0,1]
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, D == 1 ? 0xB1 : 0x4E, 0xF, 0xF, false);
+#else
+  return bk.shfl(v, (bk.tid() & (kWave - 1)) ^ D);
+#endif
+}
+// 4x4 exchange of the pieces of a quad: lanes 4q .. 4q+3 hold the pieces of
+// the four quarters of one 64-byte segment; lane j of the quad returns plane
+// j's 64-bit word of the segment (0 D, 1 G, 2 N, 3 C).  Two moves: 32-bit
+// registers between lanes j and j ^ 2, 16-bit halves between j and j ^ 1.
+template <class BK>
+DA_HDF uint64_t quad_planes(const Piece16 &p, BK &bk) {
+  const uint32_t lane = (uint32_t)bk.tid();
+  const bool up = (lane & 2u) != 0u, odd = (lane & 1u) != 0u;
+  const uint32_t got = quad_swap<2>(up ? p.dg : p.nc, bk), keep = up ? p.nc : p.dg;
+  const uint32_t lo = up ? got : keep, hi = up ? keep : got;  // my register pair's, of lanes j & 1 and (j & 1) + 2
+  const uint32_t h0 = perm_b32(hi, lo, 0x05040100u), h1 = perm_b32(hi, lo, 0x07060302u);  // low / high halves
+  const uint32_t got2 = quad_swap<1>(odd ? h0 : h1, bk), keep2 = odd ? h1 : h0;
+  const uint32_t ev = odd ? got2 : keep2, od = odd ? keep2 : got2;  // my plane's pieces of quarters 0, 2 / 1, 3
+  return (uint64_t)perm_b32(od, ev, 0x05040100u) | ((uint64_t)perm_b32(od, ev, 0x07060302u) << 32);
+}
+
 struct AddU64 {
   DA_HD uint64_t operator()(uint64_t a, uint64_t b) const { return a + b; }
 };
@@ -803,16 +854,28 @@ struct StageRegs {
   uint32_t w[kStageRounds][4];
   bool interior;
 };
-template <class BK>
+// kEveryLane: every lane executes every round's load, the lanes past the
+// staged range loading its last unit again (never stored).  A consumer that
+// takes the rounds one by one as they land (svm_fast.h front_half) needs it:
+// the compiler sizes the wait for round i from the fewest loads any path puts
+// after it, and a lane-guarded load is one a path may skip -- with the guards,
+// the wait for round 0 was vmcnt(0), the whole tile's text.
+template <bool kEveryLane = false, class BK>
 DA_HDF void stage_issue(const uint8_t *text, uint64_t n, uint64_t tlo, StageRegs &r, BK &bk) {
-  r.interior = tlo >= (uint64_t)kPre && tlo + kTile + kPost <= n;
+  // (kEveryLane: the caller has established that the tile is interior)
+  r.interior = kEveryLane || (tlo >= (uint64_t)kPre && tlo + kTile + kPost <= n);
   if (!r.interior) return;
   const uint8_t *src = text + (tlo - kPre);
   const int t = bk.tid();
 #pragma unroll
   for (int i = 0; i < kStageRounds; ++i) {
     const int u = t + i * kFThreads;
-    if (u < kStageUnits) load16(src + 16 * u, r.w[i]);
+    if (kEveryLane) {
+      load16(src + 16 * mn<int>(u, kStageUnits - 1), r.w[i]);
+      sched_fence();  // in the rounds' order (the scheduler put round 0 behind rounds 1 to 3)
+    } else if (u < kStageUnits) {
+      load16(src + 16 * u, r.w[i]);
+    }
   }
 }
 template <class BK>

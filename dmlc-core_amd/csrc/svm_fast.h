@@ -170,7 +170,7 @@ struct Shared {  // LDS of one workgroup
   uint64_t prebad;            // pre-halo bytes outside the grammar (dirty_lines)
   uint64_t qfail[kFWaves];    // segments whose first-pass "qid:" check failed (the comment pass's plane path)
   uint32_t npass;
-  uint32_t reserved;  // unused (without it the LDS offsets move, and the kernels' schedule with them)
+  uint32_t fflag;  // an interior tile's front half: 1 a letter of "qid:" (front_commit's pass), 2 a byte outside the grammar
   uint32_t nq;     // qid runs of the tile
   uint32_t hashy;  // a byte outside the grammar: comments to blank (pass 1)
   uint32_t ndl, ndr, dgate, nseg;
@@ -946,8 +946,10 @@ DA_HD uint32_t text_word(const Tile &t, uint64_t p, At at) {
   return at(p) | (at(p + 1) << 8) | (at(p + 2) << 16) | (at(p + 3) << 24);
 }
 
+// The "qid:" tokens of segment seg's masks m (needs the staged text): cleaned
+// in m; returns the flag of a failed check.
 template <bool FM, class At>
-DA_HDF uint32_t commit_seg(const Tile &t, Shared &sh, int seg, At at, bool first, Masks m) {
+DA_HDF uint32_t seg_qid(const Tile &t, Shared &sh, int seg, At at, bool first, Masks &m) {
   uint32_t bad = 0;
   const uint64_t P0 = t.tlo + (uint64_t)seg * kSegB;
   if ((m.n & m.c) || ((m.c & 1) && P0 > 0 && is_qid_letter(at(P0 - 1)))) {  // letters: "qid:" tokens
@@ -962,6 +964,12 @@ DA_HDF uint32_t commit_seg(const Tile &t, Shared &sh, int seg, At at, bool first
       m.bad = 1;
     }
   }
+  return bad;
+}
+
+template <bool FM, class At>
+DA_HDF uint32_t commit_seg(const Tile &t, Shared &sh, int seg, At at, bool first, Masks m) {
+  uint32_t bad = seg_qid<FM>(t, sh, seg, at, first, m);
   sh.gw[2 * seg] = (uint32_t)m.g;
   sh.gw[2 * seg + 1] = (uint32_t)(m.g >> 32);
   sh.u.m.d[seg + 1] = m.d;
@@ -1010,6 +1018,176 @@ DA_HDF uint32_t classify_tile(const Tile &t, Shared &sh, int tid, At at, bool fi
     atomic_or_u64(&sh.u.m.c[0], bc << (4 * tid));
   }
   return bad;
+}
+
+// ---- The front half of an interior tile (StageRegs::interior): staging and
+// classification in one phase, from the staging registers.  Unit u = tid +
+// kFThreads * i of round i covers stage bytes [16u, 16u + 16), so the quad of
+// threads 4q .. 4q + 3 holds the four quarters of stage segment q +
+// kFThreads / 4 * i, which is plane slot of the same number: the pre-halo is
+// round 0 of threads 0 .. 3.  Each thread stores its unit to the staged text,
+// classifies it as soon as that round's load has landed, and the quad
+// exchanges the pieces (fast_common.h quad_planes) so that lane j stores plane
+// j's word: no read-back of the text, no barrier between staging and
+// classification, no lane with more than its 64 bytes (and one of the tail).
+//
+// The tail -- the tile's last segment (slot kFThreads; its text is round 4 of
+// threads 0 .. 3) and the 16 bytes after the tile (gw[2 kFThreads]) -- goes to
+// the tile's last wave a byte a lane, loaded for that alone (tail_issue): four
+// ballots are the segment's planes, one more the post-halo's digit word, with
+// nothing to exchange.
+constexpr int kFrontRounds = kTile / 16 / kFThreads;  // rounds whose units every thread classifies
+static_assert(kFrontRounds * kFThreads * 16 == kTile && kFThreads % 4 == 0 && kFrontRounds < kStageRounds,
+              "whole rounds of whole quads, and the tail's text in a round after them");
+struct TailRegs {
+  uint32_t seg, post;  // last wave, lane l: byte l of the tile's last segment, byte l % 16 after the tile
+};
+template <class BK>
+DA_HDF void tail_issue(const uint8_t *text, uint64_t tlo, TailRegs &r, BK &bk) {  // an interior tile's
+  const int l = bk.tid() - (kFThreads - kWave);
+  r.seg = r.post = ' ';
+  if (l >= 0) {  // wave-uniform
+    r.seg = gbyte(text, tlo + kTile - kSegB + (uint64_t)l);
+    r.post = gbyte(text, tlo + kTile + (uint64_t)(l & 15));
+  }
+}
+
+// All threads, between the barrier that makes the class table visible and the
+// one that closes the phase.  What needs the staged text of other threads --
+// the "qid:" token checks -- is left to front_commit: Shared::fflag says
+// whether there is any.
+template <bool FM, class BK>
+DA_HDF void front_half(const Tile &t, Shared &sh, const StageRegs &r, const TailRegs &tr, BK &bk) {
+  const int tid = bk.tid(), j = tid & 3;
+  uint32_t out = 0, let = 0;  // bit i: round i's piece holds a byte outside the grammar; letters of "qid:"
+  bool lead0 = false;
+  // where lane j's plane keeps slot 0's word: D, G (the digit-plane words: segment s - 1's at gw[2 s - 2]), N, C
+  constexpr size_t kOffD = offsetof(Shared, u) + offsetof(Planes, d), kOffN = offsetof(Shared, u) + offsetof(Planes, n);
+  constexpr size_t kOffC = offsetof(Shared, u) + offsetof(Planes, c), kOffG = offsetof(Shared, gw) - 8;
+  static_assert(offsetof(Shared, gw) % 8 == 0, "a segment's two digit-plane words are one aligned 8 bytes");
+  uint8_t *plane = reinterpret_cast<uint8_t *>(&sh) + (j == 0 ? kOffD : j == 1 ? kOffG : j == 2 ? kOffN : kOffC);
+#pragma unroll
+  for (int i = 0; i < kFrontRounds; ++i) {
+    const int u = tid + i * kFThreads, s = u >> 2;
+    memcpy(sh.c.text + 16 * u, r.w[i], 16);
+    const Piece16 p = classify16_lut(r.w[i], sh.cls);
+    const uint32_t po = (p.dg >> 16) & ~p.dg;  // G without D
+    out |= (po != 0u ? 1u : 0u) << i;
+    let |= p.nc & (p.nc >> 16);
+    if (i == 0 && s == 0) {  // the pre-halo (dirty_lines' prebad; its first ':' may end a token)
+      if (!FM && po) atomic_or_u64(&sh.prebad, (uint64_t)po << (16 * j));
+      lead0 = !FM && j == 0 && ((p.nc >> 16) & 1u);
+    }
+    const uint64_t w = quad_planes(p, bk);
+    if (j != 1 || s > 0) memcpy(plane + 8 * s, &w, 8);  // (no digit-plane words for the pre-halo)
+  }
+  // units of the rounds after them (the tile's last segment, the post-halo): staged as stage_commit does
+#pragma unroll
+  for (int i = kFrontRounds; i < kStageRounds; ++i) {
+    const int u = tid + i * kFThreads;
+    if (u < kStageUnits) memcpy(sh.c.text + 16 * u, r.w[i], 16);
+  }
+  if (lead0 && is_qid_letter(gbyte(t.a->text, t.tlo - kSegB - 1))) let |= 1u;
+  uint32_t tout = 0, tlet = 0;
+  if (tid >= kFThreads - kWave) {  // the tail (wave-uniform)
+    const uint32_t x = sh.cls[cls_index(tr.seg)], y = sh.cls[cls_index(tr.post)];
+    const uint64_t D = bk.ballot((x & 0x00000001u) != 0u), G = bk.ballot((x & 0x00000100u) != 0u);
+    const uint64_t N = bk.ballot((x & 0x00010000u) != 0u), C = bk.ballot((x & 0x01000000u) != 0u);
+    // (classify_dword_lut's g: a byte >= 0x80 is no digit of a window)
+    const uint64_t P = bk.ballot((y & 0x00000100u) != 0u && tr.post < 0x80u);
+    const int l = tid - (kFThreads - kWave);
+    if (l == 0) {
+      sh.u.m.d[kFThreads] = D;
+      sh.gw[2 * kFThreads - 2] = (uint32_t)G;
+      sh.gw[2 * kFThreads - 1] = (uint32_t)(G >> 32);
+      sh.gw[2 * kFThreads] = (uint32_t)P & 0xFFFFu;
+    } else if (l == 1) {
+      sh.u.m.n[kFThreads] = N;
+      sh.u.m.c[kFThreads] = C;
+    }
+    tout = (G & ~D) != 0;
+    tlet = (N & C) != 0;
+  }
+  // bytes outside the grammar: the flag, and the segments holding some (one
+  // bit per quad and round; the pre-halo counts through prebad)
+  if (bk.ballot(out != 0u) != 0 || tout) {  // wave-uniform
+    uint32_t cnt = tout;
+#pragma unroll
+    for (int i = 0; i < kFrontRounds; ++i) {
+      uint64_t q = bk.ballot(((out >> i) & 1u) != 0u);
+      q |= q >> 1;
+      q |= q >> 2;
+      q &= 0x1111111111111111ull;
+      if (i == 0 && tid < kWave) q &= ~1ull;
+      cnt += (uint32_t)popc64(q);
+    }
+    if ((tid & (kWave - 1)) == 0) {
+      atomic_or_u32(&sh.fflag, 2u);
+      if (!FM) {
+        sh.hashy = 1;
+        if (cnt) atomic_add_u32(&sh.nseg, cnt);
+      }
+    }
+  }
+  if ((bk.ballot(let != 0u) != 0 || tlet) && (tid & (kWave - 1)) == 0) atomic_or_u32(&sh.fflag, 1u);
+}
+
+// After the barrier that closes front_half: each thread's grammar flag, and --
+// in a tile with a letter of "qid:" -- commit_seg's token checks on the planes
+// of its segment, written back, with one more barrier.  Thread 0 also takes
+// the pre-halo's, four bytes at a time as classify_tile's lanes do (a run of
+// letters is judged from each piece's first letter).
+template <bool FM, class BK, class At>
+DA_HDF uint32_t front_commit(const Tile &t, Shared &sh, BK &bk, At at) {
+  const uint32_t ff = sh.fflag;  // block-uniform
+  if (__builtin_expect(ff == 0u, 1)) return 0u;
+  const int tid = bk.tid();
+  Masks m;
+  m.d = sh.u.m.d[tid + 1];
+  m.n = sh.u.m.n[tid + 1];
+  m.c = sh.u.m.c[tid + 1];
+  m.g = sh.gw[2 * tid] | ((uint64_t)sh.gw[2 * tid + 1] << 32);
+  m.hi = 0u;
+  m.bad = (m.g & ~m.d) != 0;
+  uint32_t bad = 0;
+  if (ff & 1u) {
+    const bool was = m.bad != 0;
+    const uint64_t n0 = m.n, c0 = m.c, g0 = m.g;
+    bad = seg_qid<FM>(t, sh, tid, at, true, m);
+    if (m.n != n0) sh.u.m.n[tid + 1] = m.n;
+    if (m.c != c0) sh.u.m.c[tid + 1] = m.c;
+    if (m.g != g0) {
+      sh.gw[2 * tid] = (uint32_t)m.g;
+      sh.gw[2 * tid + 1] = (uint32_t)(m.g >> 32);
+    }
+    if (!FM && m.bad && !was) {  // strays alone: the segment counts now
+      sh.hashy = 1;
+      atomic_add_u32(&sh.nseg, 1u);
+    }
+    if (!FM && tid == 0) {
+      uint64_t pn = sh.u.m.n[0], pc = sh.u.m.c[0], st = 0;
+      auto wd = [&](uint64_t p) -> uint32_t { return text_word(t, p, at); };
+      for (int q = 0; q < 16; ++q) {
+        uint64_t bn = (pn >> (4 * q)) & 0xFu, bc = (pc >> (4 * q)) & 0xFu;
+        if (!((bn & bc) || (bc & 1))) continue;
+        const uint64_t P0 = t.tlo - kSegB + 4 * q;
+        const bool lead = is_qid_letter(at(P0 - 1));
+        uint64_t stray = 0;
+        if ((bn & bc) || lead) (void)qid_clean(P0, &bn, &bc, lead, at, wd, &stray);
+        st |= stray << (4 * q);
+        pn = (pn & ~(0xFull << (4 * q))) | (bn << (4 * q));
+        pc = (pc & ~(0xFull << (4 * q))) | (bc << (4 * q));
+      }
+      sh.u.m.n[0] = pn;
+      sh.u.m.c[0] = pc;
+      if (st) {
+        sh.hashy = 1;
+        sh.prebad |= st;
+      }
+    }
+    bk.sync();
+  }
+  return bad | m.bad;
 }
 
 // CSR stores
@@ -1642,40 +1820,77 @@ DA_HDF void tile_body(const FastSvmArgs &a, Shared &sh, BK &bk, uint32_t k) {
   t.sh = &sh;
   t.tlo = (uint64_t)k * kTile;
   t.thi = mn<uint64_t>(t.tlo + kTile, a.n);
-  // wave 0: the window of unit starts, issued ahead of the text loads so that
-  // the wait for it leaves them in flight (fast_common.h chunk_guess_begin)
-  ChunkProbe cp;
-  if (tid < kWave) cp = chunk_guess_begin(a.cs, a.nchunk, a.n, t.tlo, bk);
-  StageRegs sr;
-  stage_issue(a.text, a.n, t.tlo, sr, bk);  // its kStageRounds loads follow the window load
-  // the tile's chunk list, made in the shadow of the text loads; its readers
-  // come after the stage barrier
-  if (tid < kWave) chunk_guess_end(a.cs, a.nchunk, t.tlo, t.thi, cp, sr.interior, sh.c, bk);
-  FAST_STAMP(k, 11);
-  if (tid == 0) {
-    sh.u.m.d[0] = sh.u.m.n[0] = sh.u.m.c[0] = 0;
-    sh.nq = 0;
-    for (int w = 0; w < kFWaves; ++w) sh.qfail[w] = 0;
-    sh.hashy = 0;
-    sh.prebad = 0;
-    sh.ndl = sh.ndr = sh.nseg = sh.dgate = 0;
-  }
-  init_tables(sh, bk);
-  stage_commit(a.text, a.n, t.tlo, sr, sh.c, bk);
-  FAST_STAMP(k, 10);  // wave 0 is at the stage barrier: its own text has landed and is stored
-  bk.sync();
-  FAST_STAMP(k, 2);
-  // ---- classify: segment tid -> slot tid+1; lanes 0..15 also one word each
-  // of the 64 bytes before the tile -> slot 0
+  // thread 0's resets and the tables, between the loads' issue and the first barrier
+  auto tables = [&]() {
+    if (tid == 0) {
+      sh.u.m.d[0] = sh.u.m.n[0] = sh.u.m.c[0] = 0;
+      sh.nq = 0;
+      for (int w = 0; w < kFWaves; ++w) sh.qfail[w] = 0;
+      sh.hashy = 0;
+      sh.prebad = 0;
+      sh.fflag = 0;
+      sh.ndl = sh.ndr = sh.nseg = sh.dgate = 0;
+    }
+    init_tables(sh, bk);
+  };
   // a text byte (0 outside the text) for the qid token checks: staged, or
   // from global memory before the staged bytes
   auto at = [&](uint64_t p) -> uint32_t {
     if (p >= a.n) return 0u;
     return p + kPre >= t.tlo ? (uint32_t)sh.c.text[p - t.tlo + kPre] : gbyte(a.text, p);
   };
-  uint32_t bad = classify_tile<FM>(t, sh, tid, at, true, 7u);
-  FAST_STAMP(k, 9);
-  bk.sync();
+  uint32_t bad;
+  // (the staging registers live in this branch alone: held across the join with the other one they were spilled)
+  if (t.tlo >= (uint64_t)kPre && t.tlo + kTile + kPost <= a.n) {  // block-uniform: StageRegs::interior
+    // wave 0: the window of unit starts, issued ahead of the text loads
+    // (fast_common.h chunk_guess_begin).  Each branch issues and waits for its
+    // own: the window's register is one still being loaded until the
+    // hand-written wait of chunk_guess_end, and with one load ahead of the
+    // branch and a wait on each side the compiler copied it ahead of the edge
+    // branch's wait.
+    ChunkProbe cp;
+    if (tid < kWave) cp = chunk_guess_begin(a.cs, a.nchunk, a.n, t.tlo, bk);
+    // the tail's bytes next: every wait for a round of the text then counts the loads behind that round alone
+    TailRegs tr;
+    tail_issue(a.text, t.tlo, tr, bk);
+    StageRegs sr;
+    stage_issue<true>(a.text, a.n, t.tlo, sr, bk);  // every lane, every round: the rounds are waited for one by one
+    tables();
+    // ---- stage and classify in one phase, from the staging registers
+    // (front_half).  The class table's barrier comes first, ahead of every
+    // wait on memory, so that each wave takes its rounds as they land.  Wave 0
+    // makes the tile's chunk list after its rounds -- the window of unit
+    // starts, loaded ahead of the text, has long landed; its readers come
+    // after the barrier that closes the phase -- so that the search's
+    // registers are not needed while the staging registers are held.
+    bk.sync();
+    front_half<FM>(t, sh, sr, tr, bk);
+    FAST_STAMP(k, 11);  // wave 0's own rounds have landed, are stored and classified
+    if (tid < kWave) chunk_guess_end(a.cs, a.nchunk, t.tlo, t.thi, cp, false, sh.c, bk);
+    FAST_STAMP(k, 10);
+    bk.sync();
+    FAST_STAMP(k, 2);
+    bad = front_commit<FM>(t, sh, bk, at);
+    FAST_STAMP(k, 9);
+  } else {
+    // ---- the first tile, tiles at the end of the text: stage, then classify
+    // from LDS: segment tid -> slot tid+1; lanes 0..15 also one word each of
+    // the 64 bytes before the tile -> slot 0
+    // (no text load in flight: the window is waited for right behind its issue, then the tables, as ever)
+    if (tid < kWave) {
+      ChunkProbe cp = chunk_guess_begin(a.cs, a.nchunk, a.n, t.tlo, bk);
+      chunk_guess_end(a.cs, a.nchunk, t.tlo, t.thi, cp, false, sh.c, bk);
+    }
+    FAST_STAMP(k, 11);
+    tables();
+    stage(a.text, a.n, t.tlo, sh.c, bk);
+    FAST_STAMP(k, 10);  // wave 0 is at the stage barrier: its own text has landed and is stored
+    bk.sync();
+    FAST_STAMP(k, 2);
+    bad = classify_tile<FM>(t, sh, tid, at, true, 7u);
+    FAST_STAMP(k, 9);
+    bk.sync();
+  }
   // a byte outside the grammar ('#' among them) in the tile or in the pre-halo:
   // blank the comments and classify again (block-uniform, libsvm only)
   if (!FM && __builtin_expect(sh.hashy != 0, 0)) {

@@ -63,11 +63,13 @@ def main():
             print("  %-14s mean %8.0f cyc  p50 %8.0f  p99 %8.0f" % (PHASES[i], col.mean(), np.median(col),
                                                                    np.percentile(col, 99)))
         print("  total          mean %8.0f cyc" % d.sum(axis=1).mean())
-        if mode == "full":  # sub-phases (thread 0, wave 0): the stage phase up to the chunk list written (window
-            # load, text loads issued, partial wait, list), then to wave 0's own text stored, then its wait at
-            # the stage barrier for waves 1-3; classify compute / barrier
-            for name, a0, a1 in (("  issue+chunk list", 1, 11), ("  own text+commit", 11, 10), ("  stage barrier", 10, 2),
-                                 ("  classify body", 2, 9), ("  classify barrier", 9, 3)):
+        if mode == "full":  # sub-phases (thread 0, wave 0) of an interior tile, whose stage and classify phases
+            # are one (svm_fast.h front_half): loads issued, tables, the class table's barrier and wave 0's four
+            # rounds stored, classified and exchanged as they land; then its chunk list; then its wait at the
+            # barrier that closes the phase for waves 1-3; the token checks after it (nothing in a tile without
+            # letters).  The main rows' 'stage' ends at that barrier, 'classify' is what follows it.
+            for name, a0, a1 in (("  issue+front half", 1, 11), ("  chunk list", 11, 10), ("  phase barrier", 10, 2),
+                                 ("  front commit", 2, 9), ("  to the roles", 9, 3)):
                 col = st[:, a1] - st[:, a0]
                 print("  %-18s mean %8.0f cyc  p50 %8.0f" % (name, col.mean(), np.median(col)))
         if mode == "full":  # the slowest tiles (e.g. the comment / dirty-line pass) and their successors' wait
